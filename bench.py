@@ -34,6 +34,13 @@ CNN engine), ``--model resnet18|resnet50|vit_b16`` (BASELINE configs 3-5).  The
 reference-equivalent baseline (fp32 eager, pickle, per-layer FedAvg) is measured
 by ``scripts/reference_baseline.py``.
 
+A plain run sets up, warms up, times the K rounds and prints the result line
+(plus one summary line per rank on stderr).  ``--dump-outputs DIR`` also writes
+the model the last timed round produced as ``DIR/<parameter>.npy``; the inputs
+(weights, shards, shuffles) are seeded, so two builds can be compared output for
+output.  ``--full`` adds the reports the headline does not need: every tracer
+span per round, each rank's per-round breakdown, the kernel choice per shape.
+
 Launch: ``python bench.py --gpus N`` starts N worker processes itself (the
 launcher never touches the GPU); under ``torchrun`` each process is one rank.
 """
@@ -267,6 +274,8 @@ def run_gossip(args, env: _Env) -> dict:
     marks = {}
     round_ends = {}
 
+    outputs = {}
+
     def hook(state) -> None:
         r = state.round
         round_ends[r] = time.perf_counter()
@@ -274,6 +283,11 @@ def run_gossip(args, env: _Env) -> dict:
             _sync(env.device)
             env.barrier()
             marks[r] = time.perf_counter()
+            if r == W + K and args.dump_outputs:
+                # what the last timed round left a caller of the node with: the
+                # aggregated model (taken after the end mark, so it is not timed)
+                for name, t in state.learner.get_parameters().items():
+                    outputs[name] = t.detach().to("cpu", torch.float32).numpy().copy()
 
     node.round_hooks.append(hook)
     node.start()
@@ -318,7 +332,8 @@ def run_gossip(args, env: _Env) -> dict:
         # per-round phase breakdown from the tracer (this rank, timed rounds)
         sp = lambda name: [s for s in logger.tracer.spans(node.addr, name) if s.start >= marks[W]]  # noqa: E731
         ph = {k: sum(s.duration for s in sp(k)) / max(1, K) * 1e3 for k in ("evaluate", "fit", "wait_aggregation", "aggregate")}
-        if os.environ.get("P2PFL_BENCH_SPANS"):
+        full = args.full or bool(os.environ.get("P2PFL_BENCH_SPANS"))
+        if full:
             tot: dict = {}
             for s in logger.tracer.spans(node.addr):
                 if s.start >= marks[W]:
@@ -326,7 +341,7 @@ def run_gossip(args, env: _Env) -> dict:
             print(f"[bench rank {env.rank}] all spans, ms per round: "
                   + ", ".join(f"{k} {v / max(1, K) * 1e3:.2f}" for k, v in sorted(tot.items(), key=lambda kv: -kv[1])),
                   file=sys.stderr, flush=True)
-        if N > 1 or os.environ.get("P2PFL_BENCH_SPANS"):
+        if full:
             _print_round_breakdown(env.rank, node.addr, logger.tracer, round_ends, W, K)
         pushes = logger.tracer.counters(node.addr)
         stats = dict(plane.stats) if plane is not None else {}
@@ -340,7 +355,7 @@ def run_gossip(args, env: _Env) -> dict:
         )
         from p2pfl_amd.ops import autotune
 
-        if env.rank == 0 and autotune.choices():
+        if full and env.rank == 0 and autotune.choices():
             n_nat = sum(1 for v, _ in autotune.choices().values() if v.startswith("native"))
             print(f"[bench rank 0] kernel choice per shape (native vs library, ms): {n_nat}/{len(autotune.choices())} native\n"
                   + autotune.summary(), file=sys.stderr, flush=True)
@@ -353,7 +368,7 @@ def run_gossip(args, env: _Env) -> dict:
         node.stop()
     return {
         "elapsed": elapsed, "desc": desc, "data_desc": data_desc, "n_train": n_train, "n_val": n_val, "n_test": n_test,
-        "total": per_peer_total, "parallelism": "gossip-p2p",
+        "total": per_peer_total, "parallelism": "gossip-p2p", "outputs": outputs,
         "transport": f"xgmi/{backend_used}" + ("+split-hosts-rehearsal" if os.environ.get("NCCL_HOSTID") else ""),
     }
 
@@ -389,6 +404,31 @@ def _print_round_breakdown(rank, addr, tracer, round_ends, W, K) -> None:
               + ", ".join(f"->{p} {v / 1e6:.1f} MB" for p, v in sorted(links.items())), file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much (the contract allows 64 MB)
+
+
+def dump_outputs(out_dir: str, outputs: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write the last timed round's model as ``out_dir/<parameter name>.npy`` (float32).
+
+    A model larger than the budget is written as a fixed sample: every tensor keeps
+    the same fraction of its elements, at sorted flat indices drawn from a generator
+    seeded with the tensor's position -- the same indices in every run and build."""
+    import numpy as np
+
+    if not outputs:
+        raise RuntimeError("--dump-outputs: the last timed round left no model to write")
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in outputs.values())
+    keep = min(1.0, budget / total)
+    for i, (name, a) in enumerate(outputs.items()):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if keep < 1.0:
+            n = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng(1234 + i).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name.replace(os.sep, "_") + ".npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -406,6 +446,12 @@ def main() -> None:
     ap.add_argument("--allow-fallback", action="store_true",
                     help="let the data plane degrade from RCCL to host-staged gloo instead of failing (the JSON "
                          "'transport' then says xgmi/gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds, write the model the last one produced as DIR/<parameter>.npy (float32; "
+                         "a fixed seeded sample where the model exceeds the size budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need (stderr): every tracer span per round, the "
+                         "per-round breakdown of each rank, the kernel choice per shape")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -421,6 +467,8 @@ def main() -> None:
     ms_per_round = res["elapsed"] / args.steps * 1e3
     total = res["total"]
     per_peer = total / env.world
+    if env.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"])
     if env.rank == 0:
         print(
             json.dumps(

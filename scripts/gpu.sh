@@ -61,7 +61,7 @@ run_mode() {
     models)
       local k=${1:-3}
       for m in resnet18 resnet50 vit_b16; do
-        step 300 "bench_$m" python -u bench.py --model $m --steps "$k" --warmup 1
+        step 300 "bench_$m" python -u bench.py --model $m --steps "$k" --warmup 1 --full
       done ;;
     rehearsal)
       for n in ${@:-2 4 8}; do

@@ -443,11 +443,11 @@ def test_bench_reports_the_backend_actually_used():
     run fails instead of producing a mislabelled number."""
     base = [sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--impl", "torch",
             "--number-sub", "400", "--watchdog", "240", "--plane-backend", "rccl"]
-    r = subprocess.run(base + ["--allow-fallback"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=560)
+    r = subprocess.run(base + ["--allow-fallback", "--full"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     rec = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][0]
     assert rec["transport"] == "xgmi/gloo"
-    # per-rank, per-round breakdown on stderr at N > 1
+    # per-rank, per-round breakdown on stderr with --full
     assert any("round 1: wall" in ln and "pushes: ack" in ln for ln in r.stderr.splitlines()), r.stderr[-3000:]
     r = subprocess.run(base, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=560)
     assert r.returncode != 0

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(NT, NBUF == 1 ? 3 : (NBUF == 2 ? 2 : 1)) void conv_
   gemm_body<Tile128, NBUF, LA, LB, BN, EPI>(p, la, lb, tiles_m, tiles_n, smem);
 }
 
-// 64 x 64 output tiles (variant bit 14, kConvT64): four 32 x 32 waves; a k-major
+// 64 x 64 output tiles (kConvT64): four 32 x 32 waves; a k-major
 // operand stages only its 64 rows (8 KB per half), so the forward's 4-stage ring is
 // 64 KB -- two workgroups per CU -- and a 16x16 / 8x8 / 4x4 stage fills the chip
 // with tiles instead of split-K slices (no slab reduce launch).  No BatchNorm
@@ -304,9 +304,9 @@ __global__ __launch_bounds__(NT, NBUF >= 3 ? 2 : 4) void conv64_kernel(GemmParam
 
 template <class LA, class LB, int EPI>
 static void launch_e64(const GemmParams& p, const LA& la, const LB& lb, int grid, int tm, int tn, hipStream_t s) {
-  if (p.variant & 4096)
+  if (p.variant & kVarRing)
     hipLaunchKernelGGL((conv64_kernel<4, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
-  else if (p.variant & 8)
+  else if (p.variant & kVarSingleBuf)
     hipLaunchKernelGGL((conv64_kernel<1, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
   else
     hipLaunchKernelGGL((conv64_kernel<2, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
@@ -314,9 +314,9 @@ static void launch_e64(const GemmParams& p, const LA& la, const LB& lb, int grid
 
 template <class LA, class LB, int BN, int EPI>
 static void launch_e(const GemmParams& p, const LA& la, const LB& lb, int grid, int tm, int tn, hipStream_t s) {
-  if (p.variant & 4096)  // 4-stage ring, one workgroup per CU: short-K / small-grid shapes
+  if (p.variant & kVarRing)  // 4-stage ring, one workgroup per CU: short-K / small-grid shapes
     hipLaunchKernelGGL((conv_kernel<4, LA, LB, BN, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
-  else if (p.variant & 8)
+  else if (p.variant & kVarSingleBuf)
     hipLaunchKernelGGL((conv_kernel<1, LA, LB, BN, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
   else
     hipLaunchKernelGGL((conv_kernel<2, LA, LB, BN, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);

@@ -419,18 +419,18 @@ void register_conv(pybind11::module& m) {
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("stride"), pybind11::arg("pad"), pybind11::arg("xscale"),
         pybind11::arg("part"), pybind11::arg("dw"));
   m.def("conv_fwd", &conv_fwd, "implicit-GEMM conv forward (NHWC bf16)", arg("x"), arg("w"), arg("stride"), arg("pad"),
-        arg("dil"), arg("y"), arg("splits") = 1, arg("variant") = 10, arg("ws") = pybind11::none(),
+        arg("dil"), arg("y"), arg("splits") = 1, arg("variant") = p2::kVarAPanel | p2::kVarSingleBuf, arg("ws") = pybind11::none(),
         arg("counters") = pybind11::none());
   m.def("conv_dgrad", &conv_dgrad, "implicit-GEMM conv input gradient", arg("dy"), arg("w"), arg("stride"), arg("pad"),
-        arg("dil"), arg("dx"), arg("dx_shape"), arg("splits") = 1, arg("variant") = 10, arg("ws") = pybind11::none(),
+        arg("dil"), arg("dx"), arg("dx_shape"), arg("splits") = 1, arg("variant") = p2::kVarAPanel | p2::kVarSingleBuf, arg("ws") = pybind11::none(),
         arg("counters") = pybind11::none());
   m.def("conv_dgrad_s2", &conv_dgrad_s2, "stride-2 conv input gradient by output phase (phase-major out)", arg("dy"),
-        arg("w"), arg("pad"), arg("out"), arg("dx_shape"), arg("splits") = 1, arg("variant") = 10,
+        arg("w"), arg("pad"), arg("out"), arg("dx_shape"), arg("splits") = 1, arg("variant") = p2::kVarAPanel | p2::kVarSingleBuf,
         arg("ws") = pybind11::none(), arg("counters") = pybind11::none());
   m.def("phase_interleave", &phase_interleave, "phase-major stride-2 input gradient -> NHWC dX", arg("src"), arg("dx"),
         arg("pad"), arg("kh") = 3, arg("kw") = 3);
   m.def("conv_wgrad", &conv_wgrad, "implicit-GEMM conv weight gradient", arg("dy"), arg("x"), arg("kh"), arg("kw"),
-        arg("stride"), arg("pad"), arg("dil"), arg("out"), arg("splits") = 1, arg("variant") = 2,
+        arg("stride"), arg("pad"), arg("dil"), arg("out"), arg("splits") = 1, arg("variant") = p2::kVarAPanel,
         arg("ws") = pybind11::none(), arg("counters") = pybind11::none());
   m.def("slab_sum", &slab_sum, "sum of fp32 split-K slabs", arg("slabs"), arg("out"));
 }

@@ -73,20 +73,38 @@ struct GemmParams {
   float* ws;      // split-K workspace for the in-launch reduction
   int* counters;  // per-tile arrival counters (see above), or null
   BnEpi bn;       // BatchNorm statistics epilogue when bn.part != null
-  int variant;  // tuning experiments: bit0 setprio around MFMAs, bit1 A-panel tile order, bit2 no XCD remap, bit3 single LDS buffer (4 workgroups / CU), bit4/bit5 timing probes (no stores / no K loop), bit6 256 x 256 tile (8 waves), bit7 no DMA after the prologue (probe), bit8 legacy panel tile order instead of grouped (bit1 then picks A- vs B-panel order), bits 9-10 where the double-buffer prefetch is issued (0 before the K-tile's fragment reads, 1 after the first ones, 2 one chunk per k-substep), bit11 the ping-pong 256 x 256 pipeline of gemm_pp.hip (continuous per-phase DMA, staggered wave halves); with bit 11, bits 12-15 are the ping-pong kernel's timing probes (gemm_pp.hip).  Bit 12 is also the conv kernels' 4-stage ring (conv.hip), whose split-K slabs are 128 x 128 tiles
+  int variant;    // kernel selection and tuning bits: the kVar* constants below
 };
 
-// conv.hip variant bit 14: 64 x 64 output tiles (gemm_core.h Tile64; split-K slabs of that
-// geometry, reduced by tile_slab_reduce with the same bit).  The convolutions only -- with
-// bit 11 (the ping-pong GEMM) bit 14 is one of its timing probes.
-constexpr int kConvT64 = 1 << 14;
+// GemmParams::variant bits.  The values are part of the tuner's choice names
+// ("native:2048:6"), of P2PFL_GEMM_VARIANT and of the committed profiles.
+constexpr int kVarSetprio = 1;            // s_setprio around the core kernel's MFMA clusters
+constexpr int kVarAPanel = 2;             // consecutive tiles share an A panel (default: a B panel)
+constexpr int kVarNoXcdRemap = 4;         // workgroup ids as dispatched, no per-XCD tile runs
+constexpr int kVarSingleBuf = 8;          // 128 x 128 tile on one LDS buffer, 4 workgroups per CU
+constexpr int kVarProbeNoStore = 16;      // core kernel timing probe (wrong results): no C stores
+constexpr int kVarProbeNoKLoop = 32;      // core kernel timing probe (wrong results): no K loop
+constexpr int kVarTile256 = 64;           // 256 x 256 tile, 8 waves, on the core pipeline
+constexpr int kVarProbeNoDma = 128;       // core kernel timing probe (wrong results): no DMA after the prologue
+constexpr int kVarLegacyOrder = 256;      // plain panel tile order instead of grouped (kVarAPanel picks the panel)
+constexpr int kVarPrefetchShift = 9;      // bits 9-10: where the double buffer's prefetch is issued (0 before the
+constexpr int kVarPrefetchMask = 3 << 9;  //   K-tile's fragment reads, 1 after the first ones, 2 a chunk per k-substep)
+constexpr int kVarPP = 2048;              // the ping-pong pipeline of gemm_pp.hip (256 x 256 tile)
+constexpr int kVarRing = 4096;            // 128 x 128 tile on a 4-stage LDS ring, one workgroup per CU
+constexpr int kConvT64 = 1 << 14;         // conv.hip only: 64 x 64 tiles (gemm_core.h Tile64) and their split-K slabs
+constexpr int kVarPPM16 = 1 << 16;        // with kVarPP: v_mfma_f32_16x16x32_bf16 instead of 32x32x16
+constexpr int kVarPPStreamK = 1 << 17;    // with kVarPP: stream-K schedule, GemmParams::splits = grid size
+constexpr int kVarPPN128 = 1 << 21;       // with kVarPP: the 256 x 128 tile (gemm_pp128_kernel)
+// with kVarPP, bits 12-15 and 18-20 select nothing: the binding refuses them, so a stale
+// or forced value fails instead of reaching what bits 12 and 14 mean to the core kernels
+constexpr int kVarPPRefused = (15 << 12) | (7 << 18);
 
 void gemm_bf16(const GemmParams& p, hipStream_t s);
 // out[M][ldc] = sum of the `splits` fragment-native split-K slabs (gemm_core.h SlabGeom)
 // that a launch without counters wrote to `ws`; `variant` = that launch's (tile shape, order)
 void tile_slab_reduce(const float* ws, int splits, int M, int N, int64_t ldc, void* out, int out_bf16, int variant,
                       hipStream_t s);
-// the ping-pong pipeline (gemm_pp.hip); gemm_bf16 routes variant bit 11 here
+// the ping-pong pipeline (gemm_pp.hip); gemm_bf16 routes kVarPP here
 bool gemm_pp_supported(const GemmParams& p);
 void gemm_bf16_pp(const GemmParams& p, hipStream_t s);
 

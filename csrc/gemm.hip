@@ -8,9 +8,9 @@
 //
 // * 128 x 128 output tile per 256-thread workgroup, 4 waves as 2 x 2, each
 //   wave 64 x 64 = 2 x 2 tiles of v_mfma_f32_32x32x16_bf16, BK = 64; or
-//   (variant bit 6) 256 x 256 per 512-thread workgroup, 8 waves as 2 x 4,
+//   (kVarTile256) 256 x 256 per 512-thread workgroup, 8 waves as 2 x 4,
 //   each 128 x 64 -- half the operand bytes per FLOP, for large products;
-//   (variant bit 12) the 128 x 128 tile on a 4-stage LDS ring (3 K-tiles in
+//   (kVarRing) the 128 x 128 tile on a 4-stage LDS ring (3 K-tiles in
 //   flight, one workgroup per CU): short-K products, where a double buffer
 //   pays the L2/HBM round trip once per K-tile;
 // * the pipeline itself lives in gemm_core.h (shared with the implicit-GEMM
@@ -57,15 +57,15 @@ __global__ __launch_bounds__(Tile256::NT) void gemm256_kernel(GemmParams p, LA l
 template <int EPI, class LA, class LB>
 static void launch_e(const GemmParams& p, const LA& la, const LB& lb, hipStream_t s) {
   int tm, tn;
-  if (p.variant & 64) {
+  if (p.variant & kVarTile256) {
     const int grid = gemm_grid<Tile256>(p, tm, tn);
     hipLaunchKernelGGL((gemm256_kernel<LA, LB, EPI>), dim3(grid), dim3(Tile256::NT), 0, s, p, la, lb, tm, tn);
     return;
   }
   const int grid = gemm_grid<Tile128>(p, tm, tn);
-  if (p.variant & 4096)  // 4-stage ring (3 K-tiles in flight), one workgroup per CU: short-K products
+  if (p.variant & kVarRing)  // 4-stage ring (3 K-tiles in flight), one workgroup per CU: short-K products
     hipLaunchKernelGGL((gemm_kernel<4, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
-  else if (p.variant & 8)
+  else if (p.variant & kVarSingleBuf)
     hipLaunchKernelGGL((gemm_kernel<1, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
   else
     hipLaunchKernelGGL((gemm_kernel<2, LA, LB, EPI>), dim3(grid), dim3(NT), 0, s, p, la, lb, tm, tn);
@@ -88,7 +88,7 @@ void gemm_bf16(const GemmParams& p, hipStream_t s) {
   using namespace p2gemm;
   GemmParams q = p;
   if (q.splits < 1) q.splits = 1;
-  if ((q.variant & 2048) && gemm_pp_supported(q)) {
+  if ((q.variant & kVarPP) && gemm_pp_supported(q)) {
     gemm_bf16_pp(q, s);
     return;
   }
@@ -105,12 +105,12 @@ void gemm_bf16(const GemmParams& p, hipStream_t s) {
 void tile_slab_reduce(const float* ws, int splits, int M, int N, int64_t ldc, void* out, int out_bf16, int variant,
                       hipStream_t s) {
   using namespace p2gemm;
-  if (variant & 64) {
+  if (variant & kVarTile256) {
     const int tm = (M + 255) / 256, tn = (N + 255) / 256;
     const int64_t groups = int64_t(tm) * tn * (256 * 256 / 4);
     hipLaunchKernelGGL(tile_slab_reduce_kernel<Tile256>, dim3(int((groups + 255) / 256)), dim3(256), 0, s, ws, splits, M,
                        N, ldc, out, out_bf16, variant, tm, tn);
-  } else if ((variant & kConvT64) && !(variant & 2048)) {  // the convolutions' 64 x 64 tiles (conv.hip)
+  } else if ((variant & kConvT64) && !(variant & kVarPP)) {  // the convolutions' 64 x 64 tiles (conv.hip)
     const int tm = (M + 63) / 64, tn = (N + 63) / 64;
     const int64_t groups = int64_t(tm) * tn * (64 * 64 / 4);
     hipLaunchKernelGGL(tile_slab_reduce_kernel<Tile64>, dim3(int((groups + 255) / 256)), dim3(256), 0, s, ws, splits, M,

@@ -16,7 +16,7 @@ namespace {
 // ping-pong kernel's in-launch reduction), or the ping-pong kernel's row-major
 // M x N slabs of a separately reduced launch
 int64_t slab_elems(int64_t M, int64_t N, int64_t variant) {
-  const int64_t t = (variant & (64 | 2048)) ? 256 : 128;
+  const int64_t t = (variant & (p2::kVarTile256 | p2::kVarPP)) ? 256 : 128;
   return std::max(M * N, ((M + t - 1) / t) * ((N + t - 1) / t) * t * t);
 }
 
@@ -45,11 +45,13 @@ void gemm(torch::Tensor a, torch::Tensor b, bool a_kmajor, bool b_kmajor, torch:
   TORCH_CHECK(a_kmajor || M % 8 == 0, "gemm: an m-major A needs M % 8 == 0");
   TORCH_CHECK(M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31), "gemm: size overflow");
   TORCH_CHECK(a.device() == b.device() && out.device() == a.device(), "gemm: device mismatch");
-  // stream-K schedule of the ping-pong kernel (variant bits 11 + 17): `splits` is its grid size
-  const bool sk = (variant & 2048) && (variant & (1 << 17));
+  // stream-K schedule of the ping-pong kernel (kVarPP with kVarPPStreamK): `splits` is its grid size
+  const bool sk = (variant & p2::kVarPP) && (variant & p2::kVarPPStreamK);
   const int64_t sk_iters = ((M + 255) / 256) * ((N + 255) / 256) * ((K + 63) / 64);
-  if (variant & 2048) {
-    TORCH_CHECK(!((variant & (1 << 21)) && (splits > 1 || sk)), "gemm: the 256 x 128 ping-pong tile takes no split-K / stream-K");
+  if (variant & p2::kVarPP) {
+    TORCH_CHECK(!(variant & p2::kVarPPRefused), "gemm: variant ", variant,
+                " sets bits 12-15 / 18-20 with the ping-pong bit; they select nothing there");
+    TORCH_CHECK(!((variant & p2::kVarPPN128) && (splits > 1 || sk)), "gemm: the 256 x 128 ping-pong tile takes no split-K / stream-K");
   }
   if (sk) {
     TORCH_CHECK(splits >= 1 && splits <= sk_iters && splits <= 4096,
@@ -135,7 +137,7 @@ void tile_slab_reduce(torch::Tensor ws, int64_t splits, int64_t M, int64_t N, to
   TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kFloat32 && ws.is_contiguous() &&
                   ws.numel() >= splits * slab_elems(M, N, variant) && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0,
               "tile_slab_reduce: ws must be contiguous fp32 with splits * slab_elems(M, N) elements");
-  TORCH_CHECK(!(variant & 2048), "tile_slab_reduce: the ping-pong kernel writes row-major slabs");
+  TORCH_CHECK(!(variant & p2::kVarPP), "tile_slab_reduce: the ping-pong kernel writes row-major slabs");
   TORCH_CHECK(splits >= 1 && M >= 1 && N >= 8 && N % 4 == 0, "tile_slab_reduce: bad shape");
   TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.numel() == M * N && out.device() == ws.device() &&
                   (out.scalar_type() == torch::kFloat32 || out.scalar_type() == torch::kBFloat16) &&
@@ -149,6 +151,27 @@ void tile_slab_reduce(torch::Tensor ws, int64_t splits, int64_t M, int64_t N, to
 }  // namespace
 
 void register_gemm(pybind11::module& m) {
+  // gemm.h's variant constants under the names of p2pfl_amd/ops/variant.py
+  pybind11::dict bits;
+  bits["SETPRIO"] = p2::kVarSetprio;
+  bits["A_PANEL"] = p2::kVarAPanel;
+  bits["NO_XCD_REMAP"] = p2::kVarNoXcdRemap;
+  bits["SINGLE_BUF"] = p2::kVarSingleBuf;
+  bits["PROBE_NO_STORE"] = p2::kVarProbeNoStore;
+  bits["PROBE_NO_KLOOP"] = p2::kVarProbeNoKLoop;
+  bits["TILE256"] = p2::kVarTile256;
+  bits["PROBE_NO_DMA"] = p2::kVarProbeNoDma;
+  bits["LEGACY_ORDER"] = p2::kVarLegacyOrder;
+  bits["PREFETCH_SHIFT"] = p2::kVarPrefetchShift;
+  bits["PREFETCH_MASK"] = p2::kVarPrefetchMask;
+  bits["PP"] = p2::kVarPP;
+  bits["RING4"] = p2::kVarRing;
+  bits["T64"] = p2::kConvT64;
+  bits["PP_M16"] = p2::kVarPPM16;
+  bits["PP_SK"] = p2::kVarPPStreamK;
+  bits["PP_N128"] = p2::kVarPPN128;
+  bits["PP_REFUSED"] = p2::kVarPPRefused;
+  m.attr("gemm_variant_bits") = bits;
   m.def("tile_slab_reduce", &tile_slab_reduce, "sum of fragment-native split-K slabs into C", pybind11::arg("ws"),
         pybind11::arg("splits"), pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("out"), pybind11::arg("variant"));
   m.def("gemm", &gemm, "bf16 MFMA GEMM with fused bias/GELU/residual epilogue and split-K",

@@ -277,9 +277,9 @@ inline int epilogue_kind(const GemmParams& p) {
 
 // Output tile (tm, tn) of linear tile index t (see the tile-order note in gemm_body).
 P2_DEVICE void tile_coords(int variant, int t, int tiles_m, int tiles_n, int& tm, int& tn) {
-  if (variant & 256) {
-    tm = (variant & 2) ? t / tiles_n : t % tiles_m;
-    tn = (variant & 2) ? t % tiles_n : t / tiles_m;
+  if (variant & kVarLegacyOrder) {
+    tm = (variant & kVarAPanel) ? t / tiles_n : t % tiles_m;
+    tn = (variant & kVarAPanel) ? t % tiles_n : t / tiles_m;
   } else {
     constexpr int GROUP_M = 8;
     const int per_group = GROUP_M * tiles_n, g0 = (t / per_group) * GROUP_M;
@@ -460,7 +460,7 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / CFG::WAVES_N, wn = wave % CFG::WAVES_N;
   const int grp = tid >> 8, gt = tid & 255;  // staging group, thread within it
-  const int bid = (p.variant & 4) ? int(blockIdx.x) : xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = (p.variant & kVarNoXcdRemap) ? int(blockIdx.x) : xcd_remap(blockIdx.x, gridDim.x);
   const int tiles = tiles_m * tiles_n;
   const int split = bid / tiles, t = bid % tiles;
   // Tile order: the workgroups resident on one XCD at a time are a run of
@@ -479,7 +479,7 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
   int kper = (p.K + p.splits - 1) / p.splits;
   kper = (kper + BK - 1) / BK * BK;
   const int kb = split * kper, ke = min(p.K, kb + kper);
-  const int nt = (ke > kb && !(p.variant & 32)) ? (ke - kb + BK - 1) / BK : 0;  // bit 5: skip the K loop (timing probe)
+  const int nt = (ke > kb && !(p.variant & kVarProbeNoKLoop)) ? (ke - kb + BK - 1) / BK : 0;  // timing probe: skip the K loop
 
   f32x16 acc[FM][FN];
 #pragma unroll
@@ -512,10 +512,10 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
 #pragma unroll
       for (int q = 0; q < HB / G; ++q) dma16(lb.src(stb[q], c, k0, gt), dst + HA * HALF_A + (grp + G * q) * HALF_B + wo);
   };
-  // where the next K-tile's DMA is issued (variant bits 9-10): 0 before this
+  // where the next K-tile's DMA is issued (kVarPrefetchMask): 0 before this
   // K-tile's first fragment reads, 1 right after them, 2 spread over the four
   // k-substeps (one chunk each)
-  const int dma_mode = (p.variant >> 9) & 3;
+  const int dma_mode = (p.variant & kVarPrefetchMask) >> kVarPrefetchShift;
   // fragment rows: wave (wm, wn) owns A rows wm * 32 FM + 32 i, B rows wn * 32 FN + 32 j
   auto frag_a = [&](const char* s, int i, int ks) {
     const int r = wm * 32 * FM + 32 * i;
@@ -554,12 +554,12 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
 #pragma unroll
         for (int j = 0; j < FN; ++j) fb[cb ^ 1][j] = frag_b(s, j, ks + 1);
       }
-      if (p.variant & 1) __builtin_amdgcn_s_setprio(1);
+      if (p.variant & kVarSetprio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = mfma(fb[cb][j], fa[cb][i], acc[i][j]);
-      if (p.variant & 1) __builtin_amdgcn_s_setprio(0);
+      if (p.variant & kVarSetprio) __builtin_amdgcn_s_setprio(0);
     }
   };
   if constexpr (NBUF >= 3) {
@@ -588,7 +588,7 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
     // the other and does not drain the in-flight prefetch (vmcnt(0)) before
     // every K-tile's first fragment read -- with a runtime buffer index it
     // did, which serialised load and compute.
-    const bool dma = !(p.variant & 128);  // bit 7: no DMA after the prologue (timing probe: compute only)
+    const bool dma = !(p.variant & kVarProbeNoDma);  // no DMA after the prologue (timing probe: compute only)
     for (int it = 0; it < nt; it += 2) {
       compute(smem, (dma && it + 1 < nt) ? kb + (it + 1) * BK : -1, smem + STG);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -610,7 +610,7 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
   }
 
   // ---- epilogue: lane holds C[m][n0 + wn*32FN + j*32 + 8 g + 4 h + e] for its m
-  if (p.variant & 16) {  // bit 4: no stores (timing probe); keep acc alive
+  if (p.variant & kVarProbeNoStore) {  // no stores (timing probe); keep acc alive
     if (acc[0][0][0] == 12345.f && acc[FM - 1][FN - 1][15] == -1.f) reinterpret_cast<float*>(p.c)[0] = 0.f;
     return;
   }

@@ -29,6 +29,7 @@ from torch import nn
 
 from p2pfl_amd.ops import autotune
 from p2pfl_amd.ops.splitk import counters, slab_elems, tiles_of
+from p2pfl_amd.ops.variant import A_PANEL, RING4, SINGLE_BUF, T64
 
 # counters a test can read to prove the native path ran
 STATS = {"native_fwd": 0, "torch_fwd": 0, "gemm_1x1_fwd": 0, "stem_fwd": 0, "native_fwd_bn": 0, "bn_act_conv": 0}
@@ -46,9 +47,9 @@ _FUSED_BN = os.environ.get("P2PFL_CONV_BN_STATS", "0") == "1"
 # (default) run the implicit-GEMM kernels wherever native_ok holds
 _POLICY = autotune.policy("P2PFL_NATIVE_CONV")
 # csrc/gemm.h variant bits per product (single LDS buffer for the gathers, double buffer for split-K wgrad)
-_V_FWD = int(os.environ.get("P2PFL_CONV_VARIANT_FWD", "10"))
-_V_DGRAD = int(os.environ.get("P2PFL_CONV_VARIANT_DGRAD", "10"))
-_V_WGRAD = int(os.environ.get("P2PFL_CONV_VARIANT_WGRAD", "2"))
+_V_FWD = int(os.environ.get("P2PFL_CONV_VARIANT_FWD", str(A_PANEL | SINGLE_BUF)))
+_V_DGRAD = int(os.environ.get("P2PFL_CONV_VARIANT_DGRAD", str(A_PANEL | SINGLE_BUF)))
+_V_WGRAD = int(os.environ.get("P2PFL_CONV_VARIANT_WGRAD", str(A_PANEL)))
 
 
 def _C():
@@ -115,8 +116,8 @@ def _run_split(launch, rows: int, cols: int, s: int, out: torch.Tensor, variant:
 
 # Per-shape launch configuration.  One fixed (variant, split-K) per direction left
 # whole stages on the floor: the CIFAR ResNet's 16x16 / 8x8 stages give 128-256
-# output tiles, one workgroup per CU, and the single-LDS-buffer kernel (variant
-# bit 3, chosen for occupancy on big grids) then waits a full load latency per
+# output tiles, one workgroup per CU, and the single-LDS-buffer kernel (SINGLE_BUF,
+# chosen for occupancy on big grids) then waits a full load latency per
 # K-tile (l2 3x3 stride-2 input gradient: 21 us for 8 K-tiles, scripts/conv_one.py
 # under rocprofv3).  The first eager call of each (direction, shape) times the
 # single-buffer, double-buffer and 4-stage-ring kernels at the default split-K
@@ -124,15 +125,14 @@ def _run_split(launch, rows: int, cols: int, s: int, out: torch.Tensor, variant:
 # all-taps products) and keeps the fastest -- captured step graphs replay it.
 # P2PFL_CONV_TUNE=0: the fixed defaults.
 _TUNE = os.environ.get("P2PFL_CONV_TUNE", "1") != "0"
-_TUNE_VARIANTS = (10, 2, 4096 | 2)
-# csrc/gemm.h kConvT64: 64 x 64 output tiles (gemm_core.h Tile64).  The 16x16 / 8x8 / 4x4
+_TUNE_VARIANTS = (A_PANEL | SINGLE_BUF, A_PANEL, RING4 | A_PANEL)
+# T64 (csrc/gemm.h kConvT64): 64 x 64 output tiles (gemm_core.h Tile64).  The 16x16 / 8x8 / 4x4
 # stages get 4x the tiles of a 128 x 128 grid -- the chip fills without split-K slabs and
 # their reduce launch -- and 64-channel products stop running half of every MFMA on
 # zero columns.  Offered beside the 128 x 128 kernels (single / double buffer, 4-stage
 # ring) with its own split-K options; P2PFL_CONV_T64=0 withdraws it.
-T64 = 1 << 14
 _T64 = os.environ.get("P2PFL_CONV_T64", "1") != "0"
-_TUNE_VARIANTS_T64 = (T64 | 10, T64 | 2, T64 | 4096 | 2)
+_TUNE_VARIANTS_T64 = tuple(T64 | v for v in _TUNE_VARIANTS)
 # the 64 x 64 tiles' split-K also reduced in the launch (P2PFL_CONV_T64_IL=0: slabs + reduce only)
 _T64_IL = os.environ.get("P2PFL_CONV_T64_IL", "1") != "0"
 

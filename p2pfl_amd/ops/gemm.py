@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from p2pfl_amd.ops import autotune
 from p2pfl_amd.ops.splitk import IN_LAUNCH_MAX_SPLITS, counters, slab_elems, tiles_of
+from p2pfl_amd.ops.variant import A_PANEL, PP, PP_M16, PP_N128, PP_SK, RING4, SINGLE_BUF
 
 
 def _C():
@@ -105,10 +106,7 @@ def _product(a, b, a_kmajor, b_kmajor, dtype, splits=1):
 _VARIANT_ENV = os.environ.get("P2PFL_GEMM_VARIANT")
 
 
-PP = 2048  # variant bit 11: the ping-pong 256 x 256 pipeline (csrc/gemm_pp.hip)
-PP_M16 = 1 << 16  # with PP: the same pipeline on v_mfma_f32_16x16x32_bf16
-PP_SK = 1 << 17  # with PP: stream-K schedule, ``splits`` = grid size (csrc/gemm_pp.hip)
-PP_N128 = 1 << 21  # with PP: the 256 x 128 output tile (150 whole tiles for the N = 768 products)
+# kernel bits (PP, PP_M16, PP_SK, PP_N128, ...): ops/variant.py.  Bits of this module, never passed to the kernels:
 PP_ROWSPLIT = 1 << 22  # with PP: rows split into one full wave of 256 x 256 tiles + a 256 x 128 tail launch
 # split-K reduced in the launch (last-arriving slice per tile) at any slice count, not only up to
 # IN_LAUNCH_MAX_SPLITS: a configuration bit of this module, never passed to the kernels
@@ -142,7 +140,7 @@ def _variant(a_kmajor: bool, splits: int, M: int = 0, N: int = 0, K: int = 0, b_
         # large products: 256 x 256 tile, per-phase DMA streaming, staggered
         # wave halves (1284 vs 1106 TF/s for the round-2 256 tile at 8192^3)
         return PP
-    return 2 if (splits > 1 or not a_kmajor) else 10
+    return A_PANEL if (splits > 1 or not a_kmajor) else A_PANEL | SINGLE_BUF
 
 
 def gemm(
@@ -270,22 +268,22 @@ _NAT, _LIB = "native", "library"
 # tiles) on the ping-pong kernel or the 4-stage ring at 6-8 K-slices.
 # The stream-K schedule (PP_SK) is not offered: on every ViT product its partial-tile
 # fix-up (256 KB fp32 per workgroup, ~15-18 us of chip-wide traffic) lost to the
-# 256 x 128 tile's whole tiles (profiles/r6_vit_gemm_sweep.md, scripts/sk_anatomy.py).
+# 256 x 128 tile's whole tiles (profiles/r6_vit_gemm_sweep.md).
 def _fwd_cfgs(M: int, N: int, K: int):
     split = ((PP | PP_ROWSPLIT | PP_M16, 1), (PP | PP_ROWSPLIT, 1)) if rowsplit_rows(M, N) else ()
-    return ((PP | PP_N128, 1), (PP | PP_N128 | PP_M16, 1), (PP | PP_M16, 1), (PP, 1), (PP, 2), (10, 1), (2, 1)) + split
+    return ((PP | PP_N128, 1), (PP | PP_N128 | PP_M16, 1), (PP | PP_M16, 1), (PP, 1), (PP, 2), (A_PANEL | SINGLE_BUF, 1), (A_PANEL, 1)) + split
 
 
 def _dgrad_cfgs(M: int, N: int, K: int):
     split = ((PP | PP_ROWSPLIT | PP_M16, 1), (PP | PP_ROWSPLIT, 1)) if rowsplit_rows(M, N) else ()
-    return ((PP | PP_N128, 1), (PP | PP_N128 | PP_M16, 1), (PP, 1), (PP, 2), (2, 1), (10, 1), (2, 3)) + split
+    return ((PP | PP_N128, 1), (PP | PP_N128 | PP_M16, 1), (PP, 1), (PP, 2), (A_PANEL, 1), (A_PANEL | SINGLE_BUF, 1), (A_PANEL, 3)) + split
 
 
 # ping-pong at 3-4 slices reduces inside the launch (no slab-sum launch); at 6-8 slices
 # through a separate slab_sum pass; unsplit tiles for short reductions (the ViT's
 # class-token-only last block: K = batch rows)
-_WGRAD_CFGS = ((PP, 6), (PP, 8), (PP, 4), (PP, 3), (PP | PP_M16, 6), (10, 6), (4096 | 2, 6), (2, 3),
-                (PP | GEMM_IL, 6), (PP | GEMM_IL, 8), (4096 | 2 | GEMM_IL, 6), (2, 1), (PP, 1))
+_WGRAD_CFGS = ((PP, 6), (PP, 8), (PP, 4), (PP, 3), (PP | PP_M16, 6), (A_PANEL | SINGLE_BUF, 6), (RING4 | A_PANEL, 6),
+                (A_PANEL, 3), (PP | GEMM_IL, 6), (PP | GEMM_IL, 8), (RING4 | A_PANEL | GEMM_IL, 6), (A_PANEL, 1), (PP, 1))
 
 
 def _cfg_name(v: int, sp: int) -> str:

@@ -17,6 +17,8 @@ from typing import Dict, List, Tuple
 
 import torch
 
+from p2pfl_amd.ops.variant import PP, TILE256
+
 # Up to this many K-slices the last-arriving slice reduces a tile inside the
 # launch (<= 256 KB of partials per tile); beyond it one wide slab reduction
 # (csrc/conv.hip slab_sum) over the whole chip is faster than one workgroup
@@ -96,8 +98,8 @@ def tiles_of(rows: int, cols: int, tile: int = 128) -> int:
 
 def slab_elems(rows: int, cols: int, variant: int = 0) -> int:
     """fp32 elements of one split-K slice: fragment-native tiles of the kernel the
-    variant selects (128 x 128, or 256 x 256 with bit 6 or the ping-pong kernel's
+    variant selects (128 x 128, or 256 x 256 with TILE256 or the ping-pong kernel's
     in-launch reduction; ``csrc/gemm_core.h`` SlabGeom), or the ping-pong kernel's
     row-major rows x cols of a separately reduced launch."""
-    t = 256 if variant & (64 | 2048) else 128
+    t = 256 if variant & (TILE256 | PP) else 128
     return max(rows * cols, -(-rows // t) * -(-cols // t) * t * t)

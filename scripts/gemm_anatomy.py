@@ -5,10 +5,9 @@ times, so host launch overhead is excluded), next to hipBLASLt.
 
     python scripts/gemm_anatomy.py [--out gpurun_out/gemm_anatomy.md]
 
-Probe bits: 128-tile kernels (gemm_core.h) bit 4 no stores, bit 5 no K loop,
-bit 7 no DMA after the prologue; ping-pong (gemm_pp.hip, bit 11) bit 12 no DMA
-after the prologue, bit 13 no stagger, bit 14 no C stores, bit 15 no K loop.
-Probe timings are not correct outputs.
+Probe bits (ops/variant.py PROBE_*): the 128-tile kernels of gemm_core.h only; the
+ping-pong kernels carry none (their recorded anatomy: profiles/r3_gemm_pingpong.md,
+profiles/r5_vit_gemm_sweep.md).  Probe timings are not correct outputs.
 """
 
 from __future__ import annotations
@@ -23,6 +22,8 @@ import torch  # noqa: E402
 
 from p2pfl_amd.ops import autotune  # noqa: E402
 from p2pfl_amd.ops.gemm import gemm  # noqa: E402
+from p2pfl_amd.ops.variant import (A_PANEL, PP, PP_M16, PROBE_NO_DMA, PROBE_NO_KLOOP, PROBE_NO_STORE, RING4,  # noqa: E402
+                                   SINGLE_BUF)
 
 
 def dev_time(fn, iters=20) -> float:
@@ -38,27 +39,25 @@ def main() -> None:
     shapes = [("qkv fwd", 6304, 2304, 768), ("proj fwd", 6304, 768, 768), ("fc2 fwd", 6304, 768, 3072),
               ("fc1 fwd", 6304, 3072, 768), ("square 4096", 4096, 4096, 4096)]
     kernels = [
-        ("pingpong", 2048, {"full": 0, "no stores": 1 << 14, "no K loop": 1 << 15, "no DMA in loop": 1 << 12,
-                            "no stagger": 1 << 13}),
-        ("pingpong16", 2048 | 65536, {"full": 0, "no stores": 1 << 14, "no K loop": 1 << 15, "no DMA in loop": 1 << 12,
-                                      "no stagger": 1 << 13}),
-        ("128 dbuf", 2, {"full": 0, "no stores": 16, "no K loop": 32, "no DMA in loop": 128}),
-        ("128 1buf", 10, {"full": 0, "no stores": 16, "no K loop": 32}),
-        ("128 ring4", 4096 | 2, {"full": 0, "no stores": 16, "no K loop": 32}),
+        ("pingpong", PP, {"full": 0}),
+        ("pingpong16", PP | PP_M16, {"full": 0}),
+        ("128 dbuf", A_PANEL, {"full": 0, "no stores": PROBE_NO_STORE, "no K loop": PROBE_NO_KLOOP, "no DMA in loop": PROBE_NO_DMA}),
+        ("128 1buf", A_PANEL | SINGLE_BUF, {"full": 0, "no stores": PROBE_NO_STORE, "no K loop": PROBE_NO_KLOOP}),
+        ("128 ring4", RING4 | A_PANEL, {"full": 0, "no stores": PROBE_NO_STORE, "no K loop": PROBE_NO_KLOOP}),
     ]
-    lines = ["| product | kernel | " + " | ".join(["full", "no stores", "no K loop", "no DMA in loop", "no stagger"])
-             + " | hipBLASLt |", "|---|---|" + "---:|" * 6]
+    cols = ["full", "no stores", "no K loop", "no DMA in loop"]
+    lines = ["| product | kernel | " + " | ".join(cols) + " | hipBLASLt |", "|---|---|" + "---:|" * (len(cols) + 1)]
     for name, M, N, K in shapes:
         a = torch.randn(M, K, device="cuda").to(bf)
         b = (torch.randn(N, K, device="cuda") * 0.02).to(bf)
         lib = dev_time(lambda: torch.mm(a, b.t()))
         c = torch.empty(M, N, device="cuda", dtype=bf)
         fill = dev_time(lambda: c.fill_(1.0))
-        lines.append(f"| {name} {M}x{N}x{K} | torch fill_ of C ({M * N * 2 / 1e6:.1f} MB) | {fill:.1f} ({M * N * 2 / fill / 1e6:.2f} TB/s) | | | | | |")
+        lines.append(f"| {name} {M}x{N}x{K} | torch fill_ of C ({M * N * 2 / 1e6:.1f} MB) | {fill:.1f} ({M * N * 2 / fill / 1e6:.2f} TB/s) | | | | |")
         fl = 2.0 * M * N * K
         for kname, v, probes in kernels:
             cells = []
-            for col in ["full", "no stores", "no K loop", "no DMA in loop", "no stagger"]:
+            for col in cols:
                 if col not in probes:
                     cells.append("-")
                     continue

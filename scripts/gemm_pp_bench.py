@@ -1,4 +1,4 @@
-"""Ping-pong 256x256 GEMM (variant bit 11, csrc/gemm_pp.hip): numerics vs an fp32
+"""Ping-pong 256x256 GEMM (ops/variant.py PP, csrc/gemm_pp.hip): numerics vs an fp32
 PyTorch reference on every operand layout (tails, split-K, epilogues), then TF/s
 vs the round-2 kernels and hipBLASLt on square sizes and the ViT-B/16 products.
 
@@ -13,11 +13,12 @@ import torch  # noqa: E402
 from p2pfl_amd import ops  # noqa: E402
 from p2pfl_amd.ops.gemm import gemm_reference, splits_for  # noqa: E402
 from p2pfl_amd.ops.splitk import counters, tiles_of  # noqa: E402
+from p2pfl_amd.ops.variant import A_PANEL, PP, SINGLE_BUF, TILE256  # noqa: E402
 from scripts.gemm_bench import timeit  # noqa: E402
 
 C = ops.ext()
 bf = torch.bfloat16
-PP = 2048
+V10 = A_PANEL | SINGLE_BUF
 
 
 def check(M, N, K, ak, bk, splits=1, bias=False, gelu=False, residual=False, out_dtype=bf):
@@ -69,7 +70,7 @@ def main():
         b = (torch.rand(n, n, device="cuda") * 2 - 1).to(bf)
         o = torch.empty(n, n, device="cuda", dtype=bf)
         row = []
-        for v in (10, 64, PP):
+        for v in (V10, TILE256, PP):
             t = timeit(lambda: C.gemm(a, b, True, True, o, None, False, None, None, 1, v), iters=20, warm=3)
             row.append(f"{2 * n ** 3 / t / 1e12:.0f}")
         t = timeit(lambda: a @ b.t(), iters=20, warm=3)
@@ -92,8 +93,8 @@ def main():
         for kind, m, n, k, fn, lib in cases:
             out = torch.empty((m, n), device="cuda", dtype=bf)
             row = []
-            for v in (10, 64, PP):
-                tiles = -(-m // 256) * -(-n // 256) if v >= 64 else -(-m // 128) * -(-n // 128)
+            for v in (V10, TILE256, PP):
+                tiles = -(-m // 256) * -(-n // 256) if v & (TILE256 | PP) else -(-m // 128) * -(-n // 128)
                 best = None
                 for s in (1, 2, 3, 4):
                     if s > 1 and (kind != "wgrad" and tiles >= 200):
@@ -115,26 +116,5 @@ def main():
             print(f"| {name} {kind} {m}x{n}x{k} | " + " | ".join(row) + " |", flush=True)
 
 
-if __name__ == "__main__" and "--probes" not in sys.argv:
+if __name__ == "__main__":
     main()
-
-
-def probes():
-    """Where the ping-pong kernel's time goes: timing probes (variant bits 12-15)."""
-    names = [(PP, "full"), (PP | 4096, "no DMA"), (PP | 8192, "no stagger"), (PP | 16384, "no C stores"),
-             (PP | 32768, "no K loop"), (PP | 4096 | 16384, "no DMA, no stores"), (64, "v64"), (10, "v10")]
-    print("| shape | " + " | ".join(n for _, n in names) + " |")
-    print("|---|" + "---:|" * len(names))
-    for (m, n, k) in ((8192, 8192, 8192), (4096, 4096, 4096), (6304, 2304, 768), (6304, 3072, 768)):
-        a = (torch.rand(m, k, device="cuda") * 2 - 1).to(bf)
-        b = (torch.rand(n, k, device="cuda") * 2 - 1).to(bf)
-        o = torch.empty(m, n, device="cuda", dtype=bf)
-        row = []
-        for v, _ in names:
-            t = timeit(lambda: C.gemm(a, b, True, True, o, None, False, None, None, 1, v), iters=20, warm=3)
-            row.append(f"{t * 1e6:.1f} us / {2 * m * n * k / t / 1e12:.0f}")
-        print(f"| {m}x{n}x{k} | " + " | ".join(row) + " |", flush=True)
-
-
-if __name__ == "__main__" and "--probes" in sys.argv:
-    probes()

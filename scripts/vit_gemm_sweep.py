@@ -25,14 +25,15 @@ import torch  # noqa: E402
 from p2pfl_amd.ops import autotune  # noqa: E402
 from p2pfl_amd.ops.fused import _fx  # noqa: E402
 from p2pfl_amd.ops.gemm import gemm  # noqa: E402
+from p2pfl_amd.ops.variant import A_PANEL, PP, PP_M16, RING4, SINGLE_BUF, TILE256  # noqa: E402
 
 VARIANTS = {
-    2: "128 dbuf",
-    10: "128 1buf",
-    4096 | 2: "128 ring4",
-    64: "256 dbuf",
-    2048: "256 pingpong",
-    2048 | 65536: "256 pingpong16",
+    A_PANEL: "128 dbuf",
+    A_PANEL | SINGLE_BUF: "128 1buf",
+    RING4 | A_PANEL: "128 ring4",
+    TILE256: "256 dbuf",
+    PP: "256 pingpong",
+    PP | PP_M16: "256 pingpong16",
 }
 SPLITS = (1, 2, 3, 4, 6, 8)
 

@@ -9,6 +9,7 @@ from torch import nn
 
 from p2pfl_amd import ops
 from p2pfl_amd.ops import conv as conv_ops
+from p2pfl_amd.ops.variant import A_PANEL, RING4, SINGLE_BUF, T64
 
 pytestmark = pytest.mark.gpu
 
@@ -84,7 +85,7 @@ def test_conv_autograd_vs_fp32(N, C, H, W, O, k, s, p, d):
     assert conv.weight.grad.permute(0, 2, 3, 1).is_contiguous()
 
 
-@pytest.mark.parametrize("variant", [10, 4096 | 10])
+@pytest.mark.parametrize("variant", [A_PANEL | SINGLE_BUF, RING4 | A_PANEL | SINGLE_BUF])
 @pytest.mark.parametrize("splits", [2, 16])
 def test_conv_fwd_dgrad_split_k(splits, variant):
     """Raw split-K slabs reduced by tile_slab_reduce with the launch's own variant --
@@ -148,10 +149,10 @@ def test_conv_split_k_in_launch_reduction(splits):
 
 
 @pytest.mark.parametrize("N,C,H,W,O,k,s,p,d", CASES)
-@pytest.mark.parametrize("variant", [conv_ops.T64 | 10, conv_ops.T64 | 2, conv_ops.T64 | 4096 | 2])
+@pytest.mark.parametrize("variant", [T64 | A_PANEL | SINGLE_BUF, T64 | A_PANEL, T64 | RING4 | A_PANEL])
 @pytest.mark.parametrize("splits", [1, 3])
 def test_conv_t64_tiles_exact(N, C, H, W, O, k, s, p, d, variant, splits):
-    """64 x 64 output tiles (csrc/conv.hip conv64_kernel, variant bit 14) in all three
+    """64 x 64 output tiles (csrc/conv.hip conv64_kernel, T64) in all three
     pipelines: forward, input and weight gradient equal the fp32 products exactly on
     integer operands -- plain stores, and split-K slabs of the 64 x 64 geometry summed by
     tile_slab_reduce with the same variant (ragged M / N tails included)."""
@@ -201,7 +202,7 @@ def test_conv_t64_in_launch_split_k_exact(splits):
     N, C, H, W, O, k = 4, 128, 8, 8, 256, 3
     x, w = _operands(N, C, H, W, O, k, seed=9 * splits, integer=True)
     x4, w4 = x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1)
-    rows, v = N * H * W, conv_ops.T64 | 2
+    rows, v = N * H * W, T64 | A_PANEL
     C_ = ops.ext()
     dy = torch.randint(-2, 3, (N, O, H, W), device="cuda").to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     xr, wr = x.float().requires_grad_(), w.float().requires_grad_()

@@ -10,6 +10,7 @@ from p2pfl_amd import ops
 import importlib
 
 gemm_mod = importlib.import_module("p2pfl_amd.ops.gemm")
+from p2pfl_amd.ops.variant import A_PANEL, SINGLE_BUF, TILE256
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,8 @@ def test_gemm_layouts_vs_fp32(a_kmajor, b_kmajor, M, N, K):
         a, b = _operands(M + 8 - M % 8, N, K, a_kmajor, b_kmajor, seed=1)
         a = a[:, :M]  # an m-major [K, M] view with M % 8 != 0
         with pytest.raises(RuntimeError):
-            ops.ext().gemm(a, b, a_kmajor, b_kmajor, torch.empty(M, N, device="cuda"), None, False, None, None, 1, 10)
+            ops.ext().gemm(a, b, a_kmajor, b_kmajor, torch.empty(M, N, device="cuda"), None, False, None, None, 1,
+                           A_PANEL | SINGLE_BUF)
         return
     a, b = _operands(M, N, K, a_kmajor, b_kmajor, seed=M + N + K)
     out, _ = ops.gemm(a, b, a_kmajor, b_kmajor, out_dtype=torch.float32)
@@ -146,8 +148,8 @@ def test_vit_block_mlp_uses_native_gemm():
     torch.testing.assert_close(y.float(), ref, atol=5e-2, rtol=5e-2)
 
 
-# ---- 256 x 256 tile (variant bit 6: 8 waves, 128 x 64 per wave) -------------------------
-@pytest.mark.parametrize("variant", [64, 66])
+# ---- 256 x 256 tile (TILE256: 8 waves, 128 x 64 per wave) -------------------------
+@pytest.mark.parametrize("variant", [TILE256, TILE256 | A_PANEL])
 @pytest.mark.parametrize("a_kmajor,b_kmajor", [(True, True), (True, False), (False, True), (False, False)])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (600, 520, 200), (1000, 768, 768), (72, 1000, 96)])
 def test_gemm256_layouts_vs_fp32(monkeypatch, variant, a_kmajor, b_kmajor, M, N, K):
@@ -160,7 +162,7 @@ def test_gemm256_layouts_vs_fp32(monkeypatch, variant, a_kmajor, b_kmajor, M, N,
 
 
 def test_gemm256_exact_integers(monkeypatch):
-    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", "64")
+    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", str(TILE256))
     M, N, K = 520, 392, 256
     A = torch.randint(-3, 4, (M, K), device="cuda").to(torch.bfloat16)
     B = (torch.arange(N * K, device="cuda").view(N, K) % 7 - 3).to(torch.bfloat16)
@@ -175,7 +177,7 @@ def test_gemm256_exact_integers(monkeypatch):
 
 @pytest.mark.parametrize("splits", [2, 4, 8])
 def test_gemm256_split_k(monkeypatch, splits):
-    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", "66")
+    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", str(TILE256 | A_PANEL))
     M, N, K = 512, 768, 6304
     a, b = _operands(M, N, K, False, False, seed=splits)
     out, _ = ops.gemm(a, b, False, False, out_dtype=torch.bfloat16, splits=splits)
@@ -184,7 +186,7 @@ def test_gemm256_split_k(monkeypatch, splits):
 
 
 def test_gemm256_epilogue_bias_gelu_residual(monkeypatch):
-    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", "64")
+    monkeypatch.setattr(gemm_mod, "_VARIANT_ENV", str(TILE256))
     M, N, K = 700, 512, 192
     a, b = _operands(M, N, K, True, True, seed=5)
     bias = torch.randn(N, device="cuda")
@@ -302,7 +304,7 @@ def test_stream_k_layouts_vs_fp32(a_kmajor, b_kmajor, M, N, K, grid, m16):
     assert grid <= sk_iters(M, N, K)
     if (a_kmajor or b_kmajor) and K % 64:  # no fallback for the stream-K schedule: refused loudly
         a, b = _operands(M, N, K, a_kmajor, b_kmajor, seed=2)
-        ws = torch.empty(2 * grid * 65536, device="cuda")
+        ws = torch.empty(2 * grid * gemm_mod.SK_SLAB, device="cuda")
         cnt = torch.zeros(-(-M // 128) * -(-N // 128), dtype=torch.int32, device="cuda")
         with pytest.raises(RuntimeError, match="stream-K"):
             ops.ext().gemm(a, b, a_kmajor, b_kmajor, torch.empty(M, N, device="cuda"), None, False, None, None, grid,
@@ -336,9 +338,8 @@ def test_stream_k_epilogues(m16):
     torch.testing.assert_close(out2.float(), ref2, atol=0.5, rtol=1e-2)
 
 
-@pytest.mark.parametrize("local", [False, True], ids=["sc1", "xcd_local"])
 @pytest.mark.parametrize("grid", [96, 256])
-def test_stream_k_reused_workspace_bitwise(grid, local):
+def test_stream_k_reused_workspace_bitwise(grid):
     """Back-to-back stream-K launches over one reused counter array: every launch sees
     only its own partials (the sc1 hand-off), and the fix-up sums the partials in a
     fixed order whichever workgroup completes a tile, so repeated launches on the same
@@ -347,7 +348,7 @@ def test_stream_k_reused_workspace_bitwise(grid, local):
     from p2pfl_amd.ops.splitk import counters, tiles_of
 
     C = ops.ext()
-    V = PP | PP_SK | ((1 << 20) if local else 0)  # bit 20: XCD-local partials published with plain stores
+    V = PP | PP_SK
     M, N, K = 6304, 768, 3072  # the fc2 forward: 75 tiles of 48 K-tiles
     cnt = counters(tiles_of(M, N), torch.device("cuda"))
     ws = torch.empty(2 * grid * SK_SLAB, device="cuda")
@@ -381,7 +382,7 @@ def test_stream_k_refuses_bad_grid():
         ops.gemm(a, b, splits=sk_iters(256, 256, 128) + 1, variant=PP | PP_SK)
 
 
-# ---- 256 x 128 ping-pong tile (variant bits 11 + 21) --------------------------------------
+# ---- 256 x 128 ping-pong tile (PP | PP_N128) --------------------------------------
 @pytest.mark.parametrize("m16", [False, True], ids=["mfma32", "mfma16"])
 @pytest.mark.parametrize("a_kmajor,b_kmajor", [(True, True), (True, False), (False, True), (False, False)])
 @pytest.mark.parametrize("M,N,K", [(512, 256, 256), (296, 200, 128), (1000, 776, 448), (264, 520, 200), (6304, 768, 3072),
@@ -469,7 +470,7 @@ def test_forced_in_launch_split_k_beyond_four_slices(v_name, splits):
     import importlib
 
     g_mod = importlib.import_module("p2pfl_amd.ops.gemm")
-    v = {"pingpong": g_mod.PP, "ring": 4096 | 2}[v_name] | g_mod.GEMM_IL
+    v = {"pingpong": g_mod.PP, "ring": g_mod.RING4 | g_mod.A_PANEL}[v_name] | g_mod.GEMM_IL
     M, N, K = 768, 3072, 6304  # dW = dY^T X of the ViT-B fc products, K = tokens
     g = torch.Generator(device="cuda").manual_seed(splits)
     dy = torch.randint(-2, 3, (K, M), device="cuda", generator=g).to(torch.bfloat16)
@@ -478,3 +479,52 @@ def test_forced_in_launch_split_k_beyond_four_slices(v_name, splits):
     for _ in range(3):
         out, _ = g_mod.gemm(dy, x, False, False, out_dtype=torch.float32, splits=splits, variant=v)
         torch.testing.assert_close(out, dy.float().t() @ x.float(), atol=0, rtol=0)
+
+
+@pytest.mark.parametrize("m16", [False, True], ids=["mfma32", "mfma16"])
+def test_pingpong_exact_integers(m16):
+    """The 256 x 256 ping-pong tile, unsplit, on small integers (every partial sum at most
+    1728 in magnitude: exact in fp32): 3 x 2 tiles with M and N tails and three K-tiles (the
+    odd-count exit of the two-tile loop), every layout; the bf16 output pins the LDS
+    staging store (both sides round to nearest even)."""
+    from p2pfl_amd.ops.gemm import PP, PP_M16
+
+    v = PP | (PP_M16 if m16 else 0)
+    M, N, K = 520, 392, 192
+    A = torch.randint(-3, 4, (M, K), device="cuda").to(torch.bfloat16)
+    B = (torch.arange(N * K, device="cuda").view(N, K) % 7 - 3).to(torch.bfloat16)
+    ref = A.float() @ B.float().t()
+    for ak, bk in [(True, True), (True, False), (False, True), (False, False)]:
+        a = A if ak else A.t().contiguous()
+        b = B if bk else B.t().contiguous()
+        out, _ = ops.gemm(a, b, ak, bk, out_dtype=torch.float32, variant=v)
+        assert torch.equal(out, ref), (ak, bk)
+        outb, _ = ops.gemm(a, b, ak, bk, out_dtype=torch.bfloat16, variant=v)
+        assert torch.equal(outb, ref.to(torch.bfloat16)), (ak, bk)
+
+
+def test_pingpong_refuses_unassigned_bits():
+    """Bits 12-15 and 18-20 select nothing with the ping-pong bit: a forced or stale value
+    fails in the binding (it neither runs nor falls through to the core kernels, where
+    bit 12 is the ring and bit 14 the convolutions' 64 x 64 tile)."""
+    from p2pfl_amd.ops.gemm import PP, PP_SK, SK_SLAB
+    from p2pfl_amd.ops.splitk import counters, tiles_of
+
+    M, N, K = 256, 256, 64
+    a, b = _operands(M, N, K, True, True)
+    out = torch.empty(M, N, device="cuda")
+    with pytest.raises(RuntimeError):
+        ops.ext().gemm(a, b, True, True, out, None, False, None, None, 1, PP | (1 << 14))
+    ws = torch.empty(2 * SK_SLAB, device="cuda")
+    cnt = counters(tiles_of(M, N), torch.device("cuda"))
+    with pytest.raises(RuntimeError):
+        ops.ext().gemm(a, b, True, True, out, None, False, None, None, 1, PP | PP_SK | (1 << 20), ws, cnt)
+
+
+def test_variant_names_match_extension():
+    """csrc/gemm.h's constants, as the extension exports them, equal ops/variant.py's."""
+    from p2pfl_amd.ops import variant
+
+    names = {k: v for k, v in vars(variant).items() if k.isupper() and isinstance(v, int)}
+    assert dict(ops.ext().gemm_variant_bits) == names
+    assert (gemm_mod.PP, gemm_mod.PP_M16, gemm_mod.PP_SK, gemm_mod.PP_N128) == (2048, 1 << 16, 1 << 17, 1 << 21)

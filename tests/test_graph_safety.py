@@ -10,6 +10,7 @@ from torch import nn
 from p2pfl_amd.learning.step_graph import no_gc
 from p2pfl_amd.ops import conv as conv_ops
 from p2pfl_amd.ops.splitk import slab_elems, tiles_of
+from p2pfl_amd.ops.variant import PP, TILE256
 
 
 def test_no_gc_disables_collection_during_capture_and_restores():
@@ -31,9 +32,9 @@ def test_slab_elems_covers_fragment_native_tiles():
     assert slab_elems(128, 128) == 128 * 128
     assert slab_elems(130, 64) == tiles_of(130, 64) * 128 * 128 == 2 * 128 * 128
     assert slab_elems(6304, 768) == 50 * 6 * 128 * 128
-    # the 256 x 256 variant (bit 6) and the ping-pong kernel's row-major slabs
-    assert slab_elems(300, 300, 64) == 2 * 2 * 256 * 256
-    assert slab_elems(768, 768, 2048) >= 768 * 768
+    # the 256 x 256 tile and the ping-pong kernel's row-major slabs
+    assert slab_elems(300, 300, TILE256) == 2 * 2 * 256 * 256
+    assert slab_elems(768, 768, PP) >= 768 * 768
 
 
 def test_conv1x1_gemm_matches_conv2d_on_cpu():

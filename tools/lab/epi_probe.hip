@@ -1,6 +1,6 @@
 // Kernel lab: what does a GEMM launch with no K loop cost on the ViT output
-// shapes?  (scripts/gemm_anatomy.py: the ping-pong kernel's "no K loop" probe
-// takes 12.9 us on the 6304 x 2304 qkv output where torch's fill_ of the same
+// shapes?  (profiles/r5_vit_gemm_sweep.md: the ping-pong kernel with its K loop
+// switched off took 12.9 us on the 6304 x 2304 qkv output where torch's fill_ of the same
 // 29 MB takes 6.5 us.)  Each kernel writes a 256 x 256 bf16 tile per workgroup
 // of 512 threads (or 128 x 128 per 256 threads) of C[M][N], with 132 KB of
 // LDS declared like the real kernels.

@@ -3,7 +3,7 @@
 // Model (reference p2pfl/learning/pytorch/mnist_examples/models/cnn.py:55-98):
 //   conv5x5(1->32,"same") -> ReLU -> maxpool2 -> conv5x5(32->64,"same") -> ReLU
 //   -> maxpool2 -> flatten(3136) -> FC 3136->2048 -> ReLU -> FC 2048->10 -> CE
-// trained with Adam.  One training step is 8 kernel launches (cnn_*.hip):
+// trained with Adam.  The kernels of one training step (cnn_*.hip):
 //
 //  1 conv1_fwd         direct 5x5 conv + bias + ReLU + maxpool, input gathered
 //                      by index from the uint8 dataset (/255 folded in) -> P1 (HWC bf16) + argmax
@@ -25,8 +25,14 @@
 //                      gradient as a sparse fp32 gather at each pool1 argmax pixel;
 //                      wgrad (tap, image pair): dW2[:, :, tap] = dC2 x shifted P1
 //                      on MFMA, operands streamed from L2 -> slab per pair
+//                      conv2_bwd_fc1: the same launch hosting the first n_tiles FC1
+//                      weight-gradient + Adam tiles of 6 as extra blocks after the conv
+//                      blocks (they land on the CUs the conv roles leave idle)
 //  8 conv_adam         fixed-order slab reduction (+ conv2 bias from gB) + Adam
 //                      for the conv params + packed bf16 conv2 shadows (two layouts)
+//
+// The engine's default step is 7 launches: 1-4, route_fc2 (dA1 only), conv2_bwd_fc1
+// and fc1_conv_adam (6 from tile n_tiles on, 8 and the FC2 Adam in one launch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,6 +110,35 @@ void route_fc2_rm(const uint16_t* dH, const uint16_t* w1, const uint8_t* am2, in
 void conv2_bwd(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
                const int64_t* idx, float* wslab1, float* wslab2, int B, hipStream_t s);
 
+// The FC1 weight-gradient + Adam arguments (as fc1_wgrad_adam) of a launch that
+// hosts FC1 tiles.  Tile f of kFc1Tiles is rows 32 (f / 25), features 128 (f % 25).
+constexpr int kFc1Tiles = ((kFeat + 127) / 128) * (kHid / 32);  // 1600
+struct Fc1Args {
+  const uint16_t* dH;
+  const uint16_t* a1;
+  int mrows;
+  float* params;
+  float* m;
+  float* v;
+  float* gdump;
+  uint16_t* w1bf;
+  uint16_t* w1tbf;
+  Offsets off;
+  const int* adam_t;
+  int t_off;
+  AdamCfg cfg;
+};
+
+// conv2_bwd with FC1 tiles [0, n_tiles) as extra blocks behind the conv blocks:
+// the tiles only need route_fc2 to have finished (it reads w1bf), as conv2_bwd
+// does, and neither role touches what the other reads or writes, so nothing in
+// the launch waits.  Returns the number of tiles it hosted -- n_tiles, or 0 under
+// the measurement knob P2CNN_CONV2BWD_ROLES != 3; hosting 0 tiles is exactly
+// conv2_bwd.  Run fc1_conv_adam with first_tile = that number after it.
+int conv2_bwd_fc1(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
+                  const int64_t* idx, float* wslab1, float* wslab2, int B, const Fc1Args& f, int n_tiles,
+                  hipStream_t s);
+
 void conv_adam(const float* wslab1, const float* wslab2, const float* gb, int B, float* params, float* m, float* v,
                float* gdump, uint16_t* w2r, uint16_t* w2q, Offsets off, const int* adam_t, int t_off, AdamCfg cfg,
                hipStream_t s);
@@ -111,7 +146,8 @@ void conv_adam(const float* wslab1, const float* wslab2, const float* gb, int B,
 // conv_adam and fc1_wgrad_adam in one launch (run after conv2_bwd): the conv
 // reduction + Adam blocks hide behind the HBM-bound FC1 Adam stream.  With
 // dlogits / H non-null the FC2 gradient + Adam blocks join the launch too
-// (then route_fc2 runs with with_fc2 = false).
+// (then route_fc2 runs with with_fc2 = false).  The FC1 role covers the tiles
+// [first_tile, kFc1Tiles): the ones before ran in conv2_bwd_fc1.
 // The next step's forward inputs / outputs for fc1_conv_adam_fwd: the uint8 dataset,
 // its row indices, P1 / AM1 / P1s / A1 / AM2 buffers (A1: the other of two
 // step-parity buffers -- this launch's FC1 wgrad still reads the current one), the
@@ -137,7 +173,8 @@ void fc1_conv_adam_fwd(const uint16_t* dH, const uint16_t* a1, int mrows, const 
 void fc1_conv_adam(const uint16_t* dH, const uint16_t* a1, int mrows, const float* wslab1, const float* wslab2,
                    const float* gb, int B, float* params, float* m, float* v, float* gdump, uint16_t* w1bf,
                    uint16_t* w1tbf, uint16_t* w2r, uint16_t* w2q, Offsets off, const int* adam_t, int t_off,
-                   AdamCfg cfg, const float* dlogits, const uint16_t* H, uint16_t* w2bf, hipStream_t s);
+                   AdamCfg cfg, const float* dlogits, const uint16_t* H, uint16_t* w2bf, int first_tile,
+                   hipStream_t s);
 
 // Standalone packing of the bf16 shadows from fp32 params (after set_parameters).
 void pack_shadows(const float* params, Offsets off, uint16_t* w2r, uint16_t* w2q, uint16_t* w1bf, uint16_t* w1tbf,

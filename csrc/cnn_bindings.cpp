@@ -188,20 +188,59 @@ void k_route_fc2(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, int64_t 
   }
 }
 
-void k_conv2_bwd(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
-                 c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B) {
-  const c10::DeviceGuard g(dc2m.device());
+// conv2_bwd, optionally hosting the first n_tiles FC1 weight-gradient + Adam tiles
+// (fc = their arguments); returns the number of tiles hosted
+int64_t conv2_bwd_impl(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
+                       c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B,
+                       const p2cnn::Fc1Args& fc, int64_t n_tiles) {
   TORCH_CHECK(B >= 1 && B <= 64, "bad batch");
   TORCH_CHECK(x.numel() % 784 == 0, "x must be [N,1,28,28] uint8");
   if (!idx.has_value()) TORCH_CHECK(x.numel() / 784 >= B, "x has fewer than B rows");
-  p2cnn::conv2_bwd(reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dc2m, torch::kBFloat16, B * 64 * 224, "dc2m")),
-                   reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(p1s, torch::kBFloat16, B * p2cnn::kP1s, "p1s")),
-                   ptr<uint8_t>(am1, torch::kUInt8, B * 196 * 32, "am1"),
-                   reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2q, torch::kBFloat16, 51200, "w2q")),
-                   ptr<uint8_t>(x, torch::kUInt8, 784, "x", 1), idx_ptr(idx, B),
-                   ptr<float>(wslab1, torch::kFloat32, B * p2cnn::kDgTiles * p2cnn::kSlab1, "wslab1"),
-                   ptr<float>(wslab2, torch::kFloat32, p2cnn::wgrad_groups(int(B)) * int64_t(p2cnn::kSlab2), "wslab2"),
-                   int(B), stream());
+  return p2cnn::conv2_bwd_fc1(
+      reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dc2m, torch::kBFloat16, B * 64 * 224, "dc2m")),
+      reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(p1s, torch::kBFloat16, B * p2cnn::kP1s, "p1s")),
+      ptr<uint8_t>(am1, torch::kUInt8, B * 196 * 32, "am1"),
+      reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2q, torch::kBFloat16, 51200, "w2q")),
+      ptr<uint8_t>(x, torch::kUInt8, 784, "x", 1), idx_ptr(idx, B),
+      ptr<float>(wslab1, torch::kFloat32, B * p2cnn::kDgTiles * p2cnn::kSlab1, "wslab1"),
+      ptr<float>(wslab2, torch::kFloat32, p2cnn::wgrad_groups(int(B)) * int64_t(p2cnn::kSlab2), "wslab2"), int(B), fc,
+      int(n_tiles), stream());
+}
+
+void k_conv2_bwd(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
+                 c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B) {
+  const c10::DeviceGuard g(dc2m.device());
+  conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, p2cnn::Fc1Args{}, 0);
+}
+
+// conv2_bwd's arguments, then fc1_wgrad_adam's, then the number of FC1 tiles to host
+int64_t k_conv2_bwd_fc1(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
+                        c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B,
+                        torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::Tensor params, torch::Tensor m,
+                        torch::Tensor v, c10::optional<torch::Tensor> gdump, torch::Tensor w1bf,
+                        c10::optional<torch::Tensor> w1tbf, std::vector<int64_t> off, torch::Tensor adam_t,
+                        int64_t t_off, double lr, double b1, double b2, double eps, double wd, int64_t n_tiles) {
+  const c10::DeviceGuard g(dc2m.device());
+  TORCH_CHECK(mrows == 32 || mrows == 64, "conv2_bwd_fc1: mrows must be 32 or 64");
+  TORCH_CHECK(n_tiles >= 0 && n_tiles <= p2cnn::kFc1Tiles, "conv2_bwd_fc1: n_tiles ", n_tiles, " outside [0, ",
+              p2cnn::kFc1Tiles, "]");
+  Offsets o = offsets(off);
+  const int64_t n = params_end(o);
+  p2cnn::Fc1Args fc{};
+  fc.dH = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dH, torch::kBFloat16, mrows * 2048, "dH"));
+  fc.a1 = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(a1, torch::kBFloat16, mrows * 3136, "a1"));
+  fc.mrows = int(mrows);
+  fc.params = ptr<float>(params, torch::kFloat32, n, "params");
+  fc.m = ptr<float>(m, torch::kFloat32, n, "m");
+  fc.v = ptr<float>(v, torch::kFloat32, n, "v");
+  fc.gdump = optr<float>(gdump, torch::kFloat32, n, "gdump");
+  fc.w1bf = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1bf, torch::kBFloat16, 2048 * 3136, "w1bf"));
+  fc.w1tbf = reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf"));
+  fc.off = o;
+  fc.adam_t = ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4);
+  fc.t_off = int(t_off);
+  fc.cfg = cfg(lr, b1, b2, eps, wd);
+  return conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, fc, n_tiles);
 }
 
 void k_conv_adam(torch::Tensor wslab1, torch::Tensor wslab2, torch::Tensor gb, int64_t B, torch::Tensor params,
@@ -228,10 +267,12 @@ void k_fc1_conv_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::T
                      c10::optional<torch::Tensor> gdump, torch::Tensor w1bf, c10::optional<torch::Tensor> w1tbf, torch::Tensor w2r,
                      torch::Tensor w2q, std::vector<int64_t> off, torch::Tensor adam_t, int64_t t_off, double lr,
                      double b1, double b2, double eps, double wd, c10::optional<torch::Tensor> dlogits,
-                     c10::optional<torch::Tensor> H, c10::optional<torch::Tensor> w2bf) {
+                     c10::optional<torch::Tensor> H, c10::optional<torch::Tensor> w2bf, int64_t first_tile) {
   const c10::DeviceGuard g(params.device());
   check_batch(int(B), int(mrows));
   TORCH_CHECK(mrows <= 64, "fc1_conv_adam: mrows must be 32 or 64");
+  TORCH_CHECK(first_tile >= 0 && first_tile <= p2cnn::kFc1Tiles, "fc1_conv_adam: first_tile ", first_tile,
+              " outside [0, ", p2cnn::kFc1Tiles, "]");
   TORCH_CHECK(dlogits.has_value() == H.has_value(), "fc1_conv_adam: pass both dlogits and H or neither");
   Offsets o = offsets(off);
   const int64_t n = params_end(o);
@@ -250,7 +291,8 @@ void k_fc1_conv_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::T
       ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd),
       optr<float>(dlogits, torch::kFloat32, B * 10, "dlogits"),
       reinterpret_cast<const uint16_t*>(optr<at::BFloat16>(H, torch::kBFloat16, B * 2048, "H")),
-      reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")), stream());
+      reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")), int(first_tile),
+      stream());
 }
 
 // fc1_conv_adam + the next step's conv1 / conv2 (p2cnn::fc1_conv_adam_fwd): the same
@@ -340,13 +382,15 @@ void register_cnn(pybind11::module& m) {
         pybind11::arg("ws") = pybind11::none(), pybind11::arg("ctr") = pybind11::none());
   c.def("fc1_wgrad_adam", &k_fc1_wgrad_adam);
   c.def("conv2_bwd", &k_conv2_bwd);
+  c.def("conv2_bwd_fc1", &k_conv2_bwd_fc1,
+        "conv2_bwd hosting the first n_tiles FC1 weight-gradient + Adam tiles; returns the tiles hosted");
   c.def("conv_adam", &k_conv_adam);
   c.def("fc1_conv_adam", &k_fc1_conv_adam, pybind11::arg("dH"), pybind11::arg("a1"), pybind11::arg("mrows"), pybind11::arg("wslab1"),
         pybind11::arg("wslab2"), pybind11::arg("gb"), pybind11::arg("B"), pybind11::arg("params"), pybind11::arg("m"), pybind11::arg("v"), pybind11::arg("gdump"),
         pybind11::arg("w1bf"), pybind11::arg("w1tbf"), pybind11::arg("w2r"), pybind11::arg("w2q"), pybind11::arg("off"), pybind11::arg("adam_t"),
         pybind11::arg("t_off"), pybind11::arg("lr"), pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd"),
         pybind11::arg("dlogits") = pybind11::none(), pybind11::arg("H") = pybind11::none(),
-        pybind11::arg("w2bf") = pybind11::none());
+        pybind11::arg("w2bf") = pybind11::none(), pybind11::arg("first_tile") = 0);
   c.def("fc1_conv_adam_fwd", &k_fc1_conv_adam_fwd);
   c.def("pack_shadows", &k_pack_shadows, pybind11::arg("params"), pybind11::arg("off"), pybind11::arg("w2r"),
         pybind11::arg("w2q"), pybind11::arg("w1bf"), pybind11::arg("w1tbf"), pybind11::arg("w2bf") = pybind11::none());

@@ -918,20 +918,16 @@ P2_DEVICE void conv2_dgrad_block(int grp, int b, const uint16_t* __restrict__ dc
 }
 
 // 256-thread blocks: [0, 2B) dgrad blocks (image b = j / 2, group j % 2),
-// then wgrad blocks of 4 independent (tap, image pair) waves.
-__global__ __launch_bounds__(256) void conv2_bwd_kernel(const uint16_t* __restrict__ dc2m,
-                                                        const uint16_t* __restrict__ p1s,
-                                                        const uint8_t* __restrict__ am1,
-                                                        const uint16_t* __restrict__ w2q,
-                                                        const uint8_t* __restrict__ xds,
-                                                        const int64_t* __restrict__ idx, float* __restrict__ wslab1,
-                                                        float* __restrict__ wslab2, int B, int first_block,
-                                                        int wg_blocks, int stream_w, int wg_first) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// then wgrad blocks of 4 independent (tap, image pair) waves.  j = block id of
+// nconv conv blocks (+ first_block).
+P2_DEVICE void conv2_bwd_roles(int j, int nconv, const uint16_t* __restrict__ dc2m, const uint16_t* __restrict__ p1s,
+                               const uint8_t* __restrict__ am1, const uint16_t* __restrict__ w2q,
+                               const uint8_t* __restrict__ xds, const int64_t* __restrict__ idx,
+                               float* __restrict__ wslab1, float* __restrict__ wslab2, int B, int wg_blocks,
+                               int stream_w, int wg_first, char* smem) {
   const int nd = 2 * B;
   // wg_first: the wgrad blocks take the low block ids (dispatched first)
-  int j = blockIdx.x + first_block;
-  if (wg_first) j = j < int(gridDim.x) - nd ? j + nd : j - (int(gridDim.x) - nd);
+  if (wg_first) j = j < nconv - nd ? j + nd : j - (nconv - nd);
   if (j < nd) {
     if (stream_w)
       conv2_dgrad_block<true>(j & 1, j >> 1, dc2m, am1, w2q, xds, idx, wslab1, smem);
@@ -946,8 +942,54 @@ __global__ __launch_bounds__(256) void conv2_bwd_kernel(const uint16_t* __restri
   }
 }
 
-void conv2_bwd(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
-               const int64_t* idx, float* wslab1, float* wslab2, int B, hipStream_t s) {
+__global__ __launch_bounds__(256) void conv2_bwd_kernel(const uint16_t* __restrict__ dc2m,
+                                                        const uint16_t* __restrict__ p1s,
+                                                        const uint8_t* __restrict__ am1,
+                                                        const uint16_t* __restrict__ w2q,
+                                                        const uint8_t* __restrict__ xds,
+                                                        const int64_t* __restrict__ idx, float* __restrict__ wslab1,
+                                                        float* __restrict__ wslab2, int B, int first_block,
+                                                        int wg_blocks, int stream_w, int wg_first) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  conv2_bwd_roles(blockIdx.x + first_block, gridDim.x, dc2m, p1s, am1, w2q, xds, idx, wslab1, wslab2, B, wg_blocks,
+                  stream_w, wg_first, smem);
+}
+
+// conv2_bwd hosting FC1 weight-gradient + Adam tiles: blocks [0, nconv) are the
+// conv roles above, block nconv + f is FC1 tile f (one tile per block, the same
+// body and arithmetic as in fc1_conv_adam_kernel, which then starts at tile
+// gridDim.x - nconv).  The conv blocks fill one CU each (the launch's 143 KB of
+// LDS; a B = 32 launch has 144 of them for 256 CUs), so the dispatcher places the
+// FC1 blocks -- higher ids, one per CU as well, the LDS size being the launch's --
+// on the CUs the conv roles leave idle and on those whose dgrad blocks retire
+// first.  Both roles are ready once route_fc2 has finished and neither reads or
+// writes anything of the other's: the launch has no ordering between blocks.
+// (Measured no better, profiles/cnn_fc1_slice.md: a block walking several tiles
+// and fetching the next tile's W1 / m / v under the current one's compute and
+// stores -- about 4 us per tile either way, a lone block already moves what one
+// CU can; and the hosted stream as non-temporal accesses.)
+template <int MR>
+__global__ __launch_bounds__(256) void conv2_bwd_fc1_kernel(
+    const uint16_t* __restrict__ dc2m, const uint16_t* __restrict__ p1s, const uint8_t* __restrict__ am1,
+    const uint16_t* __restrict__ w2q, const uint8_t* __restrict__ xds, const int64_t* __restrict__ idx,
+    float* __restrict__ wslab1, float* __restrict__ wslab2, int B, int nconv, int wg_blocks, int stream_w,
+    int wg_first, Fc1Args f) {
+  static_assert(Fc1Lds<MR>::kBytes <= kDgLds, "the launch's dynamic LDS serves the FC1 role too");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int kBx = (kFeat + 127) / 128;
+  const int j = blockIdx.x;
+  if (j < nconv) {
+    conv2_bwd_roles(j, nconv, dc2m, p1s, am1, w2q, xds, idx, wslab1, wslab2, B, wg_blocks, stream_w, wg_first, smem);
+    return;
+  }
+  const int t = j - nconv;
+  fc1_wgrad_adam_body<MR>(t % kBx, t / kBx, f.dH, f.a1, f.params, f.m, f.v, f.gdump, f.w1bf, f.w1tbf, f.off, f.adam_t,
+                          f.t_off, f.cfg, smem);
+}
+
+int conv2_bwd_fc1(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
+                  const int64_t* idx, float* wslab1, float* wslab2, int B, const Fc1Args& f, int n_tiles,
+                  hipStream_t s) {
   // P2CNN_CONV2BWD_ROLES (measurement knob, read once): 1 = dgrad blocks
   // only, 2 = wgrad blocks only; unset = both (the product).  Measured
   // (scripts/kbench.py, B = 32): dgrad 7.3 us, wgrad 13.1 us, both 12.5 us.
@@ -980,8 +1022,23 @@ void conv2_bwd(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, co
   const int nd = 2 * B, nw = wg_blocks ? 5 * wgrad_groups(B) : (kTaps * wgrad_groups(B) + 3) / 4;
   const int first = roles == 2 ? nd : 0;
   const int blocks = roles == 1 ? nd : roles == 2 ? nw : nd + nw;
-  hipLaunchKernelGGL(conv2_bwd_kernel, dim3(blocks), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2,
-                     B, first, wg_blocks, stream_w, roles == 3 ? wg_first : 0);
+  // FC1 tiles are hosted only beside both conv roles; a launch hosting none is the plain kernel
+  const int na = roles == 3 ? n_tiles : 0;
+  if (na == 0)
+    hipLaunchKernelGGL(conv2_bwd_kernel, dim3(blocks), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx, wslab1,
+                       wslab2, B, first, wg_blocks, stream_w, roles == 3 ? wg_first : 0);
+  else if (f.mrows == 32)
+    hipLaunchKernelGGL(conv2_bwd_fc1_kernel<32>, dim3(blocks + na), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx,
+                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f);
+  else
+    hipLaunchKernelGGL(conv2_bwd_fc1_kernel<64>, dim3(blocks + na), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx,
+                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f);
+  return na;
+}
+
+void conv2_bwd(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
+               const int64_t* idx, float* wslab1, float* wslab2, int B, hipStream_t s) {
+  conv2_bwd_fc1(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, Fc1Args{}, 0, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1153,8 +1210,9 @@ __global__ __launch_bounds__(256) void conv_adam_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------------------
 // 7+10 in one launch (after conv2_bwd): optionally the 81 FC2 Adam blocks,
-// then the 116 conv-parameter blocks, then the 1600 FC1 weight-gradient + Adam
-// blocks.  The FC1 part streams the 6.4M-parameter Adam state (HBM-bound, ~28
+// then the 116 conv-parameter blocks, then the FC1 weight-gradient + Adam
+// blocks of tiles [f0, 1600) (the first f0 tiles rode in conv2_bwd_fc1_kernel).
+// The FC1 part streams the 6.4M-parameter Adam state (HBM-bound, ~28
 // B per parameter); the FC2 and conv parts are latency-bound reductions --
 // sharing the launch hides them behind the stream instead of paying a kernel
 // boundary and their tails.  (The FC2 role used to share route_fc2's launch:
@@ -1170,7 +1228,7 @@ __global__ __launch_bounds__(256) void fc1_conv_adam_kernel(
     float* __restrict__ v, float* __restrict__ gdump, uint16_t* __restrict__ w1bf, uint16_t* __restrict__ w1tbf,
     uint16_t* __restrict__ w2r, uint16_t* __restrict__ w2q, Offsets off, const int* __restrict__ adam_t, int t_off,
     AdamCfg cfg, const float* __restrict__ dlogits, const uint16_t* __restrict__ H, int nf2,
-    uint16_t* __restrict__ w2bf) {
+    uint16_t* __restrict__ w2bf, int f0) {
   constexpr int kLds = Fc1Lds<MR>::kBytes > kConvAdamLds ? Fc1Lds<MR>::kBytes : kConvAdamLds;
   __shared__ __attribute__((aligned(16))) char smem[kLds];
   constexpr int kCA = kC2 + kC1Blocks, kBx = (kFeat + 127) / 128;
@@ -1184,22 +1242,23 @@ __global__ __launch_bounds__(256) void fc1_conv_adam_kernel(
     conv_adam_body(j, ws1, ws2, gb, B, p, m, v, gdump, w2r, w2q, off, adam_t, t_off, cfg, smem);
     return;
   }
-  const int f = j - kCA;
+  const int f = j - kCA + f0;  // tiles [0, f0) ran in conv2_bwd_fc1
   fc1_wgrad_adam_body<MR>(f % kBx, f / kBx, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem);
 }
 
 void fc1_conv_adam(const uint16_t* dH, const uint16_t* a1, int mrows, const float* wslab1, const float* wslab2,
                    const float* gb, int B, float* params, float* m, float* v, float* gdump, uint16_t* w1bf,
                    uint16_t* w1tbf, uint16_t* w2r, uint16_t* w2q, Offsets off, const int* adam_t, int t_off,
-                   AdamCfg cfg, const float* dlogits, const uint16_t* H, uint16_t* w2bf, hipStream_t s) {
+                   AdamCfg cfg, const float* dlogits, const uint16_t* H, uint16_t* w2bf, int first_tile,
+                   hipStream_t s) {
   const int nf2 = dlogits ? kFc2Blocks256 : 0;
-  const dim3 grid(nf2 + kC2 + kC1Blocks + ((kFeat + 127) / 128) * (kHid / 32));
+  const dim3 grid(nf2 + kC2 + kC1Blocks + kFc1Tiles - first_tile);
   if (mrows == 32)
     hipLaunchKernelGGL(fc1_conv_adam_kernel<32>, grid, dim3(256), 0, s, dH, a1, wslab1, wslab2, gb, B, params, m, v,
-                       gdump, w1bf, w1tbf, w2r, w2q, off, adam_t, t_off, cfg, dlogits, H, nf2, w2bf);
+                       gdump, w1bf, w1tbf, w2r, w2q, off, adam_t, t_off, cfg, dlogits, H, nf2, w2bf, first_tile);
   else
     hipLaunchKernelGGL(fc1_conv_adam_kernel<64>, grid, dim3(256), 0, s, dH, a1, wslab1, wslab2, gb, B, params, m, v,
-                       gdump, w1bf, w1tbf, w2r, w2q, off, adam_t, t_off, cfg, dlogits, H, nf2, w2bf);
+                       gdump, w1bf, w1tbf, w2r, w2q, off, adam_t, t_off, cfg, dlogits, H, nf2, w2bf, first_tile);
 }
 
 // ---------------------------------------------------------------------------
@@ -1326,6 +1385,10 @@ void init_fwd_attributes();
 void init_attributes() {
   init_fwd_attributes();
   P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_bwd_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kDgLds));
+  P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_bwd_fc1_kernel<32>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kDgLds));
+  P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_bwd_fc1_kernel<64>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kDgLds));
   P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(route_rm_kernel<1, 1>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kRouteRmLds));

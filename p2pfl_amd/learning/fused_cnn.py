@@ -73,6 +73,12 @@ _CONV12 = os.environ.get("P2PFL_CNN_CONV12", "0") == "1"
 # cache, and their waits hold CU slots; bitwise-equal results
 # (tests/test_gpu_fused_cnn.py::test_next_forward_inside_the_adam_launch_is_bitwise_equal).
 _FWD_IN_ADAM = os.environ.get("P2PFL_CNN_FWD_IN_ADAM", "0") == "1"
+# FC1 weight-gradient + Adam tiles (of 1600) hosted by the conv2 backward launch, on
+# the CUs its 144 one-per-CU workgroups leave idle; the FC1 Adam launch starts at that
+# tile (csrc/cnn_bwd.hip conv2_bwd_fc1_kernel; profiles/cnn_fc1_slice.md).  0: the
+# plain conv2_bwd and the whole stream in fc1_conv_adam.
+FC1_SLICE_DEFAULT = 384
+FC1_TILES = 1600
 _NAMES = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "l1.weight", "l1.bias", "l2.weight", "l2.bias")
 FEAT, HID = 3136, 2048
 
@@ -91,6 +97,7 @@ class FusedCNNEngine:
         mrows: int = 32,
         arena: Optional[ModuleArena] = None,
         split_fc1: Optional[int] = None,
+        fc1_slice: Optional[int] = None,
     ) -> None:
         self.C = ops.ext().cnn
         self.C.init()
@@ -112,6 +119,10 @@ class FusedCNNEngine:
         self.S1 = int(split_fc1 if split_fc1 is not None else os.environ.get("P2PFL_CNN_FC1_SPLITS", "7"))
         if not 1 <= self.S1 <= 49:
             raise ValueError(f"FC1 split count {self.S1} outside [1, 49]")
+        # FC1 tiles hosted by the conv2 backward launch on the default step (P2PFL_CNN_FC1_SLICE)
+        self.fc1_slice = int(fc1_slice if fc1_slice is not None else os.environ.get("P2PFL_CNN_FC1_SLICE", FC1_SLICE_DEFAULT))
+        if not 0 <= self.fc1_slice <= FC1_TILES:
+            raise ValueError(f"FC1 slice {self.fc1_slice} outside [0, {FC1_TILES}]")
         dev, bf = self.device, torch.bfloat16
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
         n = self.arena.flat.numel()
@@ -222,6 +233,18 @@ class FusedCNNEngine:
         role's occupancy more than the overlap hides.  The conv-parameter Adam
         (256-thread blocks, 4 KB of LDS) does share the FC1 launch
         (``fc1_conv_adam``): it adds nothing to the FC1 role's footprint.
+        The conv2 backward launch hosts the first ``fc1_slice`` FC1 tiles
+        (``conv2_bwd_fc1``): its 144 workgroups take one CU each and leave 112
+        CUs idle for ~12.5 us, both roles are ready after route_fc2 and neither
+        touches the other's data, so -- unlike every fusion above -- nothing in
+        the launch waits.  A lone workgroup per CU moves a tile in ~4 us (about
+        what one CU can fetch), so the idle CUs take ~3 tiles each before the
+        conv roles end: 384 tiles, conv2_bwd 12.6 -> 15.0 us, the Adam launch
+        29.0 -> 23.3 us, the captured step 74.5 -> 71.3 us (scripts/kbench.py,
+        profiles/cnn_fc1_slice.md).  More tiles only lengthen the launch at
+        one workgroup per CU; bitwise-equal results for every slice.  The
+        opt-in arms below (next forward inside the Adam launch, separate Adam
+        launches) keep the plain conv2_bwd.
         """
         if B > self.mrows:
             raise ValueError(f"batch {B} > engine capacity {self.mrows}")
@@ -234,6 +257,16 @@ class FusedCNNEngine:
             C.route_fc2(self.dH, self.w1_route, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H,
                         self.params, self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, False, self.route_rm,
                         self.route_ws, self.route_ctr)
+            if nxt is None and not fwd_done and self.fc1_slice:
+                # the conv backward hosts the first FC1 tiles; the Adam launch takes the rest
+                # (not on the next-forward-in-Adam arm, whose steps pass nxt or fwd_done)
+                na = C.conv2_bwd_fc1(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B,
+                                     self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1bf,
+                                     self.w1tbf, self.off, self.adam_t, t_off, *a, self.fc1_slice)
+                C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
+                                self.gdump, self.w1bf, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
+                                self.dlogits, self.H, self.w2bf, na)
+                return
             C.conv2_bwd(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B)
             if nxt is not None and M <= 64:
                 # ... with the next step's conv1 + conv2 (nxt = its row indices and batch) in the

@@ -6,6 +6,11 @@ after one full warm-up step so every input holds realistic data.  Meant to be
 run directly or under ``rocprofv3 --pmc ... -- python3 scripts/kbench.py``.
 
     python scripts/kbench.py [--reps 200] [--only route,conv_adam]
+
+``--fc1-slice 0,256,512`` adds, per slice ``n``: the conv2 backward launch hosting
+the first ``n`` FC1 tiles (``conv2_bwd_fc1``), the merged Adam launch from tile ``n``
+(``fc2_fc1_conv_adam``), their sum, and the graph-captured step of an engine with
+``fc1_slice = n`` (``step_graph``; the figure the default is picked from).
 """
 
 from __future__ import annotations
@@ -26,6 +31,7 @@ def main() -> None:
     ap.add_argument("--only", default="")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--no-graph", action="store_true", help="skip the graph-captured step (use under --pmc)")
+    ap.add_argument("--fc1-slice", default="", help="comma-separated FC1 slices to sweep (see above)")
     args = ap.parse_args()
 
     from p2pfl_amd.learning.fused_cnn import FusedCNNEngine
@@ -68,10 +74,8 @@ def main() -> None:
         "conv_adam": lambda: C.conv_adam(eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a),
     }
     only = [s for s in args.only.split(",") if s]
-    res = {}
-    for name, fn in ks.items():
-        if only and not any(o in name for o in only):
-            continue
+
+    def timeit(fn) -> float:
         fn()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -80,9 +84,10 @@ def main() -> None:
             fn()
         e1.record()
         torch.cuda.synchronize()
-        res[name] = round(e0.elapsed_time(e1) * 1000.0 / args.reps, 2)
-    # whole step, graph-captured, for reference
-    if not only and not args.no_graph:
+        return round(e0.elapsed_time(e1) * 1000.0 / args.reps, 2)
+
+    def step_graph() -> float:
+        """One step of ``eng`` as it is configured now: 20 captured, 5 replays."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -100,10 +105,34 @@ def main() -> None:
             gr.replay()
         e1.record()
         torch.cuda.synchronize()
-        res["step_graph"] = round(e0.elapsed_time(e1) * 1000.0 / 100, 2)
+        return round(e0.elapsed_time(e1) * 1000.0 / 100, 2)
+
+    res = {}
+    for name, fn in ks.items():
+        if only and not any(o in name for o in only):
+            continue
+        res[name] = timeit(fn)
+    # whole step, graph-captured, for reference
+    if not only and not args.no_graph:
+        res["step_graph"] = step_graph()
+    slices = {}
+    for n in [int(v) for v in args.fc1_slice.split(",") if v]:
+        r = {
+            "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a, n)),
+            "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, n)),
+        }
+        r["pair"] = round(r["conv2_bwd_fc1"] + r["fc2_fc1_conv_adam"], 2)
+        if not args.no_graph:
+            keep, eng.fc1_slice = eng.fc1_slice, n
+            r["step_graph"] = step_graph()
+            eng.fc1_slice = keep
+        slices[n] = r
     if not only:
         res["sum_isolated"] = round(sum(v for k, v in res.items() if k in ("conv1_fwd", "conv2_fwd", "gemm_fc1", "head", "route_dA1_split2" if eng.route_ws is not None else "route_dA1_only", "conv2_bwd", "fc2_fc1_conv_adam")), 2)
-    print(json.dumps({"us_per_kernel": res, "batch": B}))
+    out = {"us_per_kernel": res, "batch": B}
+    if slices:
+        out["fc1_slice"] = slices
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

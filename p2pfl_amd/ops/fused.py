@@ -390,7 +390,7 @@ def attention_qkv(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     """
     B, T, C3 = qkv.shape
     C = C3 // 3
-    if _native(qkv) and qkv.dtype == torch.bfloat16 and C == heads * 64 and T <= 256:
+    if _native(qkv) and qkv.dtype == torch.bfloat16 and C == heads * 64 and 1 <= T <= 256:
         return _AttentionQKV.apply(qkv, heads)
     q, k, v = qkv.view(B, T, 3, heads, C // heads).permute(2, 0, 3, 1, 4)
     return F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T, C)

@@ -20,5 +20,5 @@ def fb():
     o.backward(g)
 both = timeit(fb, iters=50)
 fl = 4 * B * H * T * T * 64
-print(f"waves={os.environ.get('P2PFL_ATTN_WAVES', '4')}: fwd {fwd * 1e6:.1f} us ({fl / fwd / 1e12:.0f} TF/s), "
+print(f"waves={os.environ.get('P2PFL_ATTN_WAVES', '8')}: fwd {fwd * 1e6:.1f} us ({fl / fwd / 1e12:.0f} TF/s), "
       f"fwd+bwd {both * 1e6:.1f} us ({3.5 * fl / both / 1e12:.0f} TF/s)", flush=True)

@@ -6,26 +6,13 @@
 // to kMaxInputs arenas, accumulates in fp32 registers with the normalised
 // weights, and writes once.  Bytes moved = (k + 1) * 4 * n; at k = 8 and the
 // 6.5 M-parameter MNIST CNN that is 234 MB, ~40 us at the ~6 TB/s HBM3E rate.
-#include "common.h"
-#include "kernels.h"
+#include "arena_io.h"
 
 namespace p2 {
 
-struct WSumArgs {
-  const void* src[kMaxInputs];
+struct WSumArgs : ArenaSrcs {
   float w[kMaxInputs];
 };
-
-// Four consecutive elements of input k as fp32: a 16-byte fp32 load or an
-// 8-byte bf16 load widened in registers (a bf16 arena costs half the bytes).
-P2_DEVICE f32x4 load4(const void* base, int64_t i, bool bf16) {
-  if (bf16) {
-    const uint2 r = __builtin_bit_cast(uint2, __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(base) + i));
-    return f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                 __uint_as_float(r.y & 0xffff0000u)};
-  }
-  return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base) + i);
-}
 
 // bf16_mask bit k: input k is bf16 (else fp32).  The mask is uniform across
 // the grid, so the per-input dtype test never diverges.  acc_in (may alias
@@ -40,11 +27,7 @@ __global__ __launch_bounds__(256) void wsum_kernel(WSumArgs a, uint32_t bf16_mas
 #pragma unroll
     for (int k = 0; k < K; ++k) acc += a.w[k] * load4(a.src[k], i, (bf16_mask >> k) & 1u);
     acc *= scale;
-    if (out_bf16) {
-      reinterpret_cast<uint2*>(out)[i] = uint2{pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3])};
-    } else {
-      reinterpret_cast<f32x4*>(out)[i] = acc;
-    }
+    store4(out, i, acc, out_bf16);
   }
 }
 
@@ -54,15 +37,10 @@ __global__ void wsum_tail(WSumArgs a, uint32_t bf16_mask, int k, const float* ac
   if (i >= n) return;
   float acc = acc_in ? acc_in[i] : 0.f;
   for (int j = 0; j < k; ++j) {
-    const float v = ((bf16_mask >> j) & 1u) ? bf16_to_f32(reinterpret_cast<const uint16_t*>(a.src[j])[i])
-                                            : reinterpret_cast<const float*>(a.src[j])[i];
-    acc = fmaf(a.w[j], v, acc);
+    acc = fmaf(a.w[j], load1(a.src[j], i, (bf16_mask >> j) & 1u), acc);
   }
   acc *= scale;
-  if (out_bf16)
-    reinterpret_cast<uint16_t*>(out)[i] = f32_to_bf16(acc);
-  else
-    reinterpret_cast<float*>(out)[i] = acc;
+  store1(out, i, acc, out_bf16);
 }
 
 template <int K>

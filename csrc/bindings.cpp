@@ -61,6 +61,50 @@ void weighted_sum(std::vector<torch::Tensor> srcs, std::vector<double> weights, 
                    out_bf16 ? 1 : 0, n, stream());
 }
 
+// pointer / dtype tables of 1..kMaxInputs arenas of one size on one device
+struct ArenaList {
+  std::vector<const void*> ptrs;
+  std::vector<int> bf;
+  int64_t n;
+};
+ArenaList check_arenas(const std::vector<torch::Tensor>& srcs, size_t min_k, const char* op) {
+  TORCH_CHECK(srcs.size() >= min_k && srcs.size() <= size_t(p2::kMaxInputs), op, ": takes ", min_k, " to ",
+              p2::kMaxInputs, " arenas, got ", srcs.size());
+  ArenaList a;
+  a.n = srcs[0].numel();
+  for (const auto& t : srcs) {
+    check_arena(t, "src");
+    TORCH_CHECK(t.numel() == a.n, op, ": size mismatch");
+    TORCH_CHECK(t.device() == srcs[0].device(), op, ": device mismatch");
+    a.ptrs.push_back(t.data_ptr());
+    a.bf.push_back(t.scalar_type() == torch::kBFloat16 ? 1 : 0);
+  }
+  return a;
+}
+
+void trimmed_mean(std::vector<torch::Tensor> srcs, int64_t trim, torch::Tensor out) {
+  const ArenaList a = check_arenas(srcs, 1, "trimmed_mean");
+  const int k = int(srcs.size());
+  TORCH_CHECK(trim >= 0 && trim <= (k - 1) / 2, "trimmed_mean: trim must be in [0, ", (k - 1) / 2, "], got ", trim);
+  check_arena(out, "out");
+  TORCH_CHECK(out.numel() == a.n && out.device() == srcs[0].device(),
+              "trimmed_mean: out must have the inputs' size and device");
+  const c10::DeviceGuard guard(out.device());
+  p2::trimmed_mean(a.ptrs.data(), a.bf.data(), k, int(trim), out.data_ptr(),
+                   out.scalar_type() == torch::kBFloat16 ? 1 : 0, a.n, stream());
+}
+
+torch::Tensor pairwise_sqdist(std::vector<torch::Tensor> srcs) {
+  const ArenaList a = check_arenas(srcs, 2, "pairwise_sqdist");
+  const int k = int(srcs.size());
+  const c10::DeviceGuard guard(srcs[0].device());
+  const auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(srcs[0].device());
+  torch::Tensor partials = torch::empty({int64_t(k) * (k - 1) / 2, int64_t(p2::pairwise_sqdist_blocks(a.n))}, opts);
+  torch::Tensor out = torch::empty({k, k}, opts);
+  p2::pairwise_sqdist(a.ptrs.data(), a.bf.data(), k, partials.data_ptr<float>(), out.data_ptr<float>(), a.n, stream());
+  return out;
+}
+
 uint16_t* opt_bf16(const c10::optional<torch::Tensor>& t, int64_t n) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 && t->is_contiguous() && t->numel() >= n,
@@ -245,6 +289,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = scale * (acc_in + sum_i w_i * src_i) (flat arenas, fp32/bf16 in, fp32/bf16 out, fp32 running sum)",
         pybind11::arg("srcs"), pybind11::arg("weights"), pybind11::arg("out"), pybind11::arg("acc_in") = pybind11::none(),
         pybind11::arg("scale") = 1.0);
+  m.def("trimmed_mean", &trimmed_mean,
+        "out = coordinate-wise mean of up to 16 arenas after dropping the trim lowest and highest values "
+        "(trim = (k-1)/2: median)",
+        pybind11::arg("srcs"), pybind11::arg("trim"), pybind11::arg("out"));
+  m.def("pairwise_sqdist", &pairwise_sqdist,
+        "k x k fp32 matrix of squared L2 distances between 2..16 arenas, one pass, deterministic",
+        pybind11::arg("srcs"));
   m.def("adam_step", &adam_step, "fused whole-arena Adam/AdamW step");
   m.def("sgd_step", &sgd_step, "fused whole-arena SGD(+momentum/nesterov) step");
   m.def("adam_mt_step", &adam_mt_step, "multi-tensor Adam/AdamW over per-tensor grads into flat fp32 state",

@@ -17,6 +17,24 @@ constexpr int kMaxInputs = 16;
 void weighted_sum(const void* const* srcs, const int* src_bf16, const float* weights, int k, const float* acc_in,
                   float scale, void* out, int out_bf16, int64_t n, hipStream_t s);
 
+// Robust aggregation (robust_agg.hip).  Both take up to kMaxInputs arenas of n
+// elements (trimmed_mean at least 1, pairwise_sqdist at least 2), each fp32 or
+// bf16, and throw std::invalid_argument outside that range.
+//
+// out[i] = mean of the values {srcs[j][i]} left after dropping the trim lowest
+// and trim highest, 0 <= trim <= (k - 1) / 2, added in ascending order in fp32
+// (independent of the order of srcs).  trim = (k - 1) / 2 is the median (mean
+// of the two middle values for even k), trim = 0 the plain mean.
+void trimmed_mean(const void* const* srcs, const int* src_bf16, int k, int trim, void* out, int out_bf16, int64_t n,
+                  hipStream_t s);
+// out[k][k] (fp32, symmetric, zero diagonal) = squared L2 distances between
+// the arenas, each arena read once.  partials: k (k - 1) / 2 *
+// pairwise_sqdist_blocks(n) floats of workspace.  Reductions run in a fixed
+// order (no atomics): the same inputs give the bitwise-same matrix.
+int pairwise_sqdist_blocks(int64_t n);
+void pairwise_sqdist(const void* const* srcs, const int* src_bf16, int k, float* partials, float* out, int64_t n,
+                     hipStream_t s);
+
 struct AdamParams {
   float lr, beta1, beta2, eps, weight_decay;
   float step_size;     // lr / (1 - beta1^t)

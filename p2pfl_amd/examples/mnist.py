@@ -1,9 +1,10 @@
 """Decentralized MNIST: N in-process nodes train an MLP or CNN and FedAvg over gossip.
 
 Reference: p2pfl/examples/mnist.py (same flags: --nodes --rounds --epochs
---show_metrics --measure_time), plus --model, --protocol, --partition and
---device.  Data is synthetic MNIST-shaped unless P2PFL_MNIST_DIR points at the
-IDX files.  Metrics are printed as a table (no plotting dependency).
+--show_metrics --measure_time), plus --model, --protocol, --partition,
+--device and --aggregator (fedavg, or a Byzantine-robust one).  Data is
+synthetic MNIST-shaped unless P2PFL_MNIST_DIR points at the IDX files.
+Metrics are printed as a table (no plotting dependency).
 """
 
 from __future__ import annotations
@@ -16,11 +17,14 @@ from typing import List
 from p2pfl_amd.communication.grpc import GrpcCommunicationProtocol
 from p2pfl_amd.communication.memory import InMemoryCommunicationProtocol
 from p2pfl_amd.data import MnistFederatedDM
+from p2pfl_amd.learning.aggregators import FedAvg, FedMedian, Krum, TrimmedMean
 from p2pfl_amd.management.logger import logger
 from p2pfl_amd.models import CNN, MLP
 from p2pfl_amd.node import Node
 from p2pfl_amd.settings import Settings
 from p2pfl_amd.utils import wait_4_results, wait_convergence
+
+AGGREGATORS = {"fedavg": FedAvg, "fedmedian": FedMedian, "trimmed_mean": TrimmedMean, "krum": Krum}
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -35,6 +39,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--partition", choices=["iid", "label_sorted", "dirichlet"], default="iid")
     p.add_argument("--alpha", type=float, default=0.5, help="Dirichlet concentration")
     p.add_argument("--batch", type=int, default=32)
+    p.add_argument("--aggregator", choices=sorted(AGGREGATORS), default="fedavg",
+                   help="aggregation strategy of every node (trimmed_mean: trim=1, krum: f=1, m=1)")
     p.add_argument("--device", default=None, help="cpu / cuda / cuda:N (default: GPU if present)")
     p.add_argument("--fast", action="store_true", help="shrink gossip/heartbeat periods (test settings)")
     # reference flag names (p2pfl/examples/mnist.py:44-66)
@@ -63,7 +69,7 @@ def _print_metrics() -> None:
 
 def mnist(n: int, r: int, e: int, show_metrics: bool = True, measure_time: bool = False, model: str = "mlp",
           protocol: str = "memory", partition: str = "iid", alpha: float = 0.5, batch: int = 32,
-          device=None, use_unix_socket: bool = False) -> List[Node]:
+          device=None, use_unix_socket: bool = False, aggregator: str = "fedavg") -> List[Node]:
     start = time.time()
     proto = InMemoryCommunicationProtocol if protocol == "memory" else GrpcCommunicationProtocol
     nodes: List[Node] = []
@@ -72,7 +78,7 @@ def mnist(n: int, r: int, e: int, show_metrics: bool = True, measure_time: bool 
         data = MnistFederatedDM(sub_id=i, number_sub=n, batch_size=batch, partitioner=partition, alpha=alpha)
         kw = {"device": device} if device else {}
         addr = f"unix:///tmp/p2pfl_amd-{os.getpid()}-{i}.sock" if use_unix_socket else "127.0.0.1"
-        node = Node(net, data, address=addr, protocol=proto, **kw)
+        node = Node(net, data, address=addr, protocol=proto, aggregator=AGGREGATORS[aggregator], **kw)
         node.start()
         nodes.append(node)
     try:
@@ -102,7 +108,7 @@ def main(argv=None) -> None:
     else:
         Settings.LOG_LEVEL = "INFO"
     mnist(args.nodes, args.rounds, args.epochs, args.show_metrics, args.measure_time, args.model, args.protocol,
-          args.partition, args.alpha, args.batch, args.device, args.use_unix_socket)
+          args.partition, args.alpha, args.batch, args.device, args.use_unix_socket, args.aggregator)
 
 
 if __name__ == "__main__":

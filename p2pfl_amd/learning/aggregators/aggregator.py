@@ -19,7 +19,10 @@ Differences from the reference:
   be rejected anyway;
 * partial aggregations are memoised per contributor subset until the stored
   models change (gossip asks for the same subset once per neighbour per
-  iteration).
+  iteration);
+* ``partial_aggregation = False`` marks strategies that cannot be computed
+  from partial results (median, trimmed mean, Krum): their models are gossiped
+  one by one and pre-combined entries are refused.
 """
 
 from __future__ import annotations
@@ -49,6 +52,13 @@ ModelEntry = Tuple[Any, int]
 
 
 class Aggregator:
+    # False for strategies that are no function of partial results (a median
+    # of medians is not a median): their models travel one by one.  Gossip then
+    # gets single stored entries from get_partial_aggregation, never a
+    # combination, and a pre-combined entry that is not the full aggregate is
+    # rejected at intake.
+    partial_aggregation: bool = True
+
     def __init__(self, node_name: str = "unknown") -> None:
         self.node_name = node_name
         self._train_set: List[str] = []
@@ -164,6 +174,12 @@ class Aggregator:
         c = set(contributors)
         return c <= set(self._train_set) and (set(self._train_set) - self._lost) <= c
 
+    def _precombined_locked(self, contributors: List[str]) -> bool:
+        """A partial aggregate of several members, which a non-decomposable
+        strategy cannot use (e.g. pre-averaged by a peer configured with FedAvg)."""
+        return (not self.partial_aggregation and len(contributors) > 1
+                and not self._full_aggregate_locked(contributors))
+
     def uncovered(self, contributors: List[str]) -> List[str]:
         """Live train-set members a full aggregate with these contributors lacks
         (what keeps a waiting node from accepting it)."""
@@ -186,6 +202,8 @@ class Aggregator:
             if self._complete_locked():
                 return False
             if not all(n in self._train_set for n in contributors):
+                return False
+            if self._precombined_locked(contributors):
                 return False
             if len(contributors) == len(self._train_set) or self._full_aggregate_locked(contributors):
                 return True
@@ -223,6 +241,9 @@ class Aggregator:
                 return []
             if not all(n in self._train_set for n in nodes):
                 logger.debug(self.node_name, f"Can't add a model from a node ({nodes}) that is not in the training set.")
+                return []
+            if self._precombined_locked(nodes):
+                logger.debug(self.node_name, f"Can't add a partial aggregate ({nodes}): {type(self).__name__} needs single models.")
                 return []
             if len(nodes) == len(self._train_set) or self._full_aggregate_locked(nodes):
                 # a full aggregate (of every live member) supersedes the partials
@@ -277,6 +298,11 @@ class Aggregator:
             chosen = {k: v for k, v in self._models.items() if not (set(k.split()) & excl)}
             if not chosen:
                 return None, None, None
+            if not self.partial_aggregation:
+                # one stored entry as it is (the smallest key: every call with the
+                # same exclusions offers the same one); nothing to cache
+                k = min(chosen)
+                return chosen[k][0], k.split(), chosen[k][1]
             key = frozenset(chosen)
             hit = self._partial_cache.get(key)
             if hit is not None:

@@ -147,6 +147,112 @@ def weighted_average(
 
 
 # ----------------------------------------------------------------------------
+# robust aggregation (coordinate-wise order statistics, pairwise distances)
+# ----------------------------------------------------------------------------
+MAX_ROBUST_INPUTS = 16  # csrc/kernels.h kMaxInputs: one launch holds every input in registers
+
+
+def _check_robust_inputs(flats: Sequence[torch.Tensor], op: str) -> int:
+    k = len(flats)
+    if k == 0:
+        raise ValueError(f"{op}: no inputs")
+    if k > MAX_ROBUST_INPUTS:
+        raise ValueError(f"{op}: at most {MAX_ROBUST_INPUTS} inputs are supported, got {k}")
+    n = flats[0].numel()
+    for f in flats:
+        if f.numel() != n:
+            raise ValueError(f"{op}: inputs differ in size")
+        if f.device != flats[0].device:
+            raise ValueError(f"{op}: inputs are on different devices")
+    return k
+
+
+def _kernel_arenas(flats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    ok = (torch.float32, torch.bfloat16)
+    return [f if (f.dtype in ok and f.is_contiguous() and f.data_ptr() % 16 == 0) else f.float().contiguous()
+            for f in (f.reshape(-1) for f in flats)]
+
+
+def trimmed_mean_reference(flats: Sequence[torch.Tensor], trim: int) -> torch.Tensor:
+    """Per coordinate: sort the k values, drop the ``trim`` lowest and highest,
+    add the rest in ascending order in fp32 and divide by ``k - 2 * trim`` (the
+    kernel's operation sequence)."""
+    k = len(flats)
+    s = torch.stack([f.reshape(-1).float() for f in flats]).sort(0).values
+    acc = s[trim].clone()
+    for j in range(trim + 1, k - trim):
+        acc.add_(s[j])
+    return acc.div_(float(k - 2 * trim))
+
+
+def trimmed_mean(
+    flats: Sequence[torch.Tensor],
+    trim: int,
+    out: Optional[torch.Tensor] = None,
+    out_dtype: torch.dtype = torch.float32,
+) -> torch.Tensor:
+    """Coordinate-wise trimmed mean of up to 16 flat arenas (fp32 / bf16 in any
+    mix): the ``trim`` lowest and ``trim`` highest values of every coordinate
+    are dropped, ``0 <= trim <= (k - 1) // 2``.  ``trim = (k - 1) // 2`` is the
+    median (numpy's: the mean of the two middle values for even k), ``trim = 0``
+    the unweighted mean.  The result does not depend on the order of ``flats``.
+    Inputs must be finite.  One fused kernel on the GPU."""
+    k = _check_robust_inputs(flats, "trimmed_mean")
+    trim = int(trim)
+    if not 0 <= trim <= (k - 1) // 2:
+        raise ValueError(f"trimmed_mean: trim must be in [0, {(k - 1) // 2}] for {k} inputs, got {trim}")
+    n = flats[0].numel()
+    if out is not None:
+        if out.numel() != n or out.device != flats[0].device:
+            raise ValueError("trimmed_mean: out must have the inputs' size and device")
+        out_dtype = out.dtype
+    if not _gpu(flats[0]):
+        res = trimmed_mean_reference(flats, trim)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res.to(out_dtype)
+    if out is None:
+        out = torch.empty(n, dtype=out_dtype, device=flats[0].device)
+    ext().trimmed_mean(_kernel_arenas(flats), trim, out)
+    return out
+
+
+def coordinate_median(
+    flats: Sequence[torch.Tensor],
+    out: Optional[torch.Tensor] = None,
+    out_dtype: torch.dtype = torch.float32,
+) -> torch.Tensor:
+    """Coordinate-wise median: :func:`trimmed_mean` with ``trim = (k - 1) // 2``."""
+    _check_robust_inputs(flats, "coordinate_median")
+    return trimmed_mean(flats, (len(flats) - 1) // 2, out=out, out_dtype=out_dtype)
+
+
+def pairwise_sqdist_reference(flats: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``D[i, j] = sum((flats[i] - flats[j]) ** 2)`` in fp32, one pair at a time."""
+    k = len(flats)
+    x = [f.reshape(-1).float() for f in flats]
+    d = torch.zeros(k, k, dtype=torch.float32, device=x[0].device)
+    for i in range(k):
+        for j in range(i + 1, k):
+            d[i, j] = d[j, i] = (x[i] - x[j]).square().sum()
+    return d
+
+
+def pairwise_sqdist(flats: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``k x k`` fp32 matrix of squared L2 distances between up to 16 flat
+    arenas (fp32 / bf16), symmetric with a zero diagonal.  On the GPU every
+    arena is read once and all reductions run in a fixed order without atomics:
+    the same inputs in the same order give the bitwise-same matrix."""
+    k = _check_robust_inputs(flats, "pairwise_sqdist")
+    if not _gpu(flats[0]):
+        return pairwise_sqdist_reference(flats)
+    if k == 1:
+        return torch.zeros(1, 1, dtype=torch.float32, device=flats[0].device)
+    return ext().pairwise_sqdist(_kernel_arenas(flats))
+
+
+# ----------------------------------------------------------------------------
 # optimizers (whole-arena, in place)
 # ----------------------------------------------------------------------------
 def adam_step_reference(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, decoupled=False):

@@ -16,6 +16,9 @@
 //  5 route_fc2         dA1 = dH x W1 (W1^T bf16 shadow) + pool2/ReLU backward in
 //                      the epilogue -> dC2 map + fp32 bias terms;  extra blocks:
 //                      dW2 = dlogits^T H and db2 with Adam applied in place
+//                      route_rm_fc1: the row-major-W1 routing launch hosting FC1 tiles
+//                      [0, n_route) of 6 behind its 98 one-per-CU blocks; the tiles write
+//                      the W1 shadow buffer the routing blocks do not read
 //  6 fc1_wgrad_adam    dW1 = dH^T A1 on MFMA with Adam fused into the epilogue:
 //                      the 6.4 M-element gradient never touches memory; writes
 //                      W1 (fp32), m, v and both bf16 shadows (W1, W1^T)
@@ -25,14 +28,17 @@
 //                      gradient as a sparse fp32 gather at each pool1 argmax pixel;
 //                      wgrad (tap, image pair): dW2[:, :, tap] = dC2 x shifted P1
 //                      on MFMA, operands streamed from L2 -> slab per pair
-//                      conv2_bwd_fc1: the same launch hosting the first n_tiles FC1
+//                      conv2_bwd_fc1: the same launch hosting the next n_tiles FC1
 //                      weight-gradient + Adam tiles of 6 as extra blocks after the conv
 //                      blocks (they land on the CUs the conv roles leave idle)
 //  8 conv_adam         fixed-order slab reduction (+ conv2 bias from gB) + Adam
 //                      for the conv params + packed bf16 conv2 shadows (two layouts)
 //
-// The engine's default step is 7 launches: 1-4, route_fc2 (dA1 only), conv2_bwd_fc1
-// and fc1_conv_adam (6 from tile n_tiles on, 8 and the FC2 Adam in one launch).
+// The engine's default step is 7 launches: 1-4, route_rm_fc1 (dA1 + FC1 tiles
+// [0, n_route)), conv2_bwd_fc1 (FC1 tiles [n_route, n_route + n_tiles)) and
+// fc1_conv_adam (6 from tile n_route + n_tiles on, 8 and the FC2 Adam in one launch).
+// A step that hosts tiles in the routing launch reads one of two row-major W1 shadow
+// buffers and writes the other ("hops"); every tile of a step writes the same buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -121,7 +127,8 @@ struct Fc1Args {
   float* m;
   float* v;
   float* gdump;
-  uint16_t* w1bf;
+  const uint16_t* w1bf;  // the row-major W1 shadow the launch's routing role reads (null: none)
+  uint16_t* w1bf_w;      // the row-major W1 shadow the tiles write
   uint16_t* w1tbf;
   Offsets off;
   const int* adam_t;
@@ -129,15 +136,25 @@ struct Fc1Args {
   AdamCfg cfg;
 };
 
-// conv2_bwd with FC1 tiles [0, n_tiles) as extra blocks behind the conv blocks:
-// the tiles only need route_fc2 to have finished (it reads w1bf), as conv2_bwd
-// does, and neither role touches what the other reads or writes, so nothing in
-// the launch waits.  Returns the number of tiles it hosted -- n_tiles, or 0 under
-// the measurement knob P2CNN_CONV2BWD_ROLES != 3; hosting 0 tiles is exactly
-// conv2_bwd.  Run fc1_conv_adam with first_tile = that number after it.
+// conv2_bwd with FC1 tiles [first_tile, first_tile + n_tiles) as extra blocks behind
+// the conv blocks: the tiles only need route_fc2 to have finished (it reads the W1
+// shadow an in-place step's tiles rewrite), as conv2_bwd does, and neither role
+// touches what the other reads or writes, so nothing in the launch waits.  Returns
+// the number of tiles it hosted -- n_tiles, or 0 under the measurement knob
+// P2CNN_CONV2BWD_ROLES != 3; hosting 0 tiles is exactly conv2_bwd.  Run
+// fc1_conv_adam with first_tile + that number after it.
 int conv2_bwd_fc1(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
                   const int64_t* idx, float* wslab1, float* wslab2, int B, const Fc1Args& f, int n_tiles,
-                  hipStream_t s);
+                  int first_tile, hipStream_t s);
+
+// route_fc2_rm (unsplit) with FC1 tiles [0, n_tiles) as extra blocks behind the
+// routing (and FC2) blocks: the tiles need dH and A1 only, and write f.w1bf_w, which
+// must not be the shadow w1 the routing blocks read -- then nothing in the launch
+// waits.  Returns the number of tiles hosted; hosting 0 tiles is exactly route_fc2_rm.
+int route_rm_fc1(const uint16_t* dH, const uint16_t* w1, const uint8_t* am2, int mrows, int B, uint16_t* dc2m,
+                 float* gb, const float* dlogits, const uint16_t* H, float* params, float* m, float* v, float* gdump,
+                 Offsets off, const int* adam_t, int t_off, AdamCfg cfg, bool with_fc2, const Fc1Args& f, int n_tiles,
+                 hipStream_t s);
 
 void conv_adam(const float* wslab1, const float* wslab2, const float* gb, int B, float* params, float* m, float* v,
                float* gdump, uint16_t* w2r, uint16_t* w2q, Offsets off, const int* adam_t, int t_off, AdamCfg cfg,
@@ -147,7 +164,7 @@ void conv_adam(const float* wslab1, const float* wslab2, const float* gb, int B,
 // reduction + Adam blocks hide behind the HBM-bound FC1 Adam stream.  With
 // dlogits / H non-null the FC2 gradient + Adam blocks join the launch too
 // (then route_fc2 runs with with_fc2 = false).  The FC1 role covers the tiles
-// [first_tile, kFc1Tiles): the ones before ran in conv2_bwd_fc1.
+// [first_tile, kFc1Tiles): the ones before ran in route_rm_fc1 / conv2_bwd_fc1.
 // The next step's forward inputs / outputs for fc1_conv_adam_fwd: the uint8 dataset,
 // its row indices, P1 / AM1 / P1s / A1 / AM2 buffers (A1: the other of two
 // step-parity buffers -- this launch's FC1 wgrad still reads the current one), the

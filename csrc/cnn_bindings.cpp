@@ -188,11 +188,63 @@ void k_route_fc2(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, int64_t 
   }
 }
 
-// conv2_bwd, optionally hosting the first n_tiles FC1 weight-gradient + Adam tiles
-// (fc = their arguments); returns the number of tiles hosted
+// The FC1 weight-gradient + Adam arguments of a launch that hosts FC1 tiles; w1bf_w is
+// the row-major W1 shadow the tiles write.
+p2cnn::Fc1Args fc1_args(const torch::Tensor& dH, const torch::Tensor& a1, int64_t mrows, const torch::Tensor& params,
+                        const torch::Tensor& m, const torch::Tensor& v, const c10::optional<torch::Tensor>& gdump,
+                        const torch::Tensor& w1bf_w, const c10::optional<torch::Tensor>& w1tbf, const Offsets& o,
+                        const torch::Tensor& adam_t, int64_t t_off, const AdamCfg& c) {
+  const int64_t n = params_end(o);
+  p2cnn::Fc1Args fc{};
+  fc.dH = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dH, torch::kBFloat16, mrows * 2048, "dH"));
+  fc.a1 = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(a1, torch::kBFloat16, mrows * 3136, "a1"));
+  fc.mrows = int(mrows);
+  fc.params = ptr<float>(params, torch::kFloat32, n, "params");
+  fc.m = ptr<float>(m, torch::kFloat32, n, "m");
+  fc.v = ptr<float>(v, torch::kFloat32, n, "v");
+  fc.gdump = optr<float>(gdump, torch::kFloat32, n, "gdump");
+  fc.w1bf_w = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1bf_w, torch::kBFloat16, 2048 * 3136, "w1bf"));
+  fc.w1tbf = reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf"));
+  fc.off = o;
+  fc.adam_t = ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4);
+  fc.t_off = int(t_off);
+  fc.cfg = c;
+  return fc;
+}
+
+// The row-major-W1 routing launch (dA1 only or with the FC2 blocks) hosting FC1 tiles
+// [0, n_tiles): route_fc2's arguments, then A1, the W1 shadow the tiles write -- NOT the
+// one the routing blocks read (w1) -- and the tile count; returns the tiles hosted
+int64_t k_route_rm_fc1(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, int64_t mrows, int64_t B,
+                       torch::Tensor dc2m, torch::Tensor gb, torch::Tensor dlogits, torch::Tensor H, torch::Tensor params,
+                       torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> gdump, std::vector<int64_t> off,
+                       torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2, double eps, double wd,
+                       bool with_fc2, torch::Tensor a1, torch::Tensor w1_write, int64_t n_tiles) {
+  const c10::DeviceGuard g(dH.device());
+  check_batch(int(B), int(mrows));
+  TORCH_CHECK(mrows <= 64, "route_rm_fc1: mrows must be 32 or 64");
+  TORCH_CHECK(n_tiles >= 0 && n_tiles <= p2cnn::kFc1Tiles, "route_rm_fc1: n_tiles ", n_tiles, " outside [0, ",
+              p2cnn::kFc1Tiles, "]");
+  Offsets o = offsets(off);
+  p2cnn::Fc1Args fc = fc1_args(dH, a1, mrows, params, m, v, gdump, w1_write, c10::nullopt, o, adam_t, t_off,
+                               cfg(lr, b1, b2, eps, wd));
+  fc.w1bf = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1, torch::kBFloat16, 2048 * 3136, "w1"));
+  // the hazard the second shadow buffer removes: a hosted tile rewriting W1 rows a routing block still reads
+  TORCH_CHECK(n_tiles == 0 || fc.w1bf != fc.w1bf_w,
+              "route_rm_fc1: hosted FC1 tiles must write the other W1 shadow buffer than the routing blocks read");
+  return p2cnn::route_rm_fc1(
+      fc.dH, fc.w1bf, ptr<uint8_t>(am2, torch::kUInt8, B * 3136, "am2"), int(mrows), int(B),
+      reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dc2m, torch::kBFloat16, B * 64 * 224, "dc2m")),
+      ptr<float>(gb, torch::kFloat32, B * 3136, "gb"), ptr<float>(dlogits, torch::kFloat32, B * 10, "dlogits"),
+      reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(H, torch::kBFloat16, B * 2048, "H")), fc.params, fc.m, fc.v,
+      fc.gdump, o, fc.adam_t, int(t_off), fc.cfg, with_fc2, fc, int(n_tiles), stream());
+}
+
+// conv2_bwd, optionally hosting n_tiles FC1 weight-gradient + Adam tiles from first_tile
+// on (fc = their arguments); returns the number of tiles hosted
 int64_t conv2_bwd_impl(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
                        c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B,
-                       const p2cnn::Fc1Args& fc, int64_t n_tiles) {
+                       const p2cnn::Fc1Args& fc, int64_t n_tiles, int64_t first_tile) {
   TORCH_CHECK(B >= 1 && B <= 64, "bad batch");
   TORCH_CHECK(x.numel() % 784 == 0, "x must be [N,1,28,28] uint8");
   if (!idx.has_value()) TORCH_CHECK(x.numel() / 784 >= B, "x has fewer than B rows");
@@ -204,43 +256,34 @@ int64_t conv2_bwd_impl(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1,
       ptr<uint8_t>(x, torch::kUInt8, 784, "x", 1), idx_ptr(idx, B),
       ptr<float>(wslab1, torch::kFloat32, B * p2cnn::kDgTiles * p2cnn::kSlab1, "wslab1"),
       ptr<float>(wslab2, torch::kFloat32, p2cnn::wgrad_groups(int(B)) * int64_t(p2cnn::kSlab2), "wslab2"), int(B), fc,
-      int(n_tiles), stream());
+      int(n_tiles), int(first_tile), stream());
 }
 
 void k_conv2_bwd(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
                  c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B) {
   const c10::DeviceGuard g(dc2m.device());
-  conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, p2cnn::Fc1Args{}, 0);
+  conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, p2cnn::Fc1Args{}, 0, 0);
 }
 
 // conv2_bwd's arguments, then fc1_wgrad_adam's, then the number of FC1 tiles to host
+// and the first of them
 int64_t k_conv2_bwd_fc1(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1, torch::Tensor w2q, torch::Tensor x,
                         c10::optional<torch::Tensor> idx, torch::Tensor wslab1, torch::Tensor wslab2, int64_t B,
                         torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::Tensor params, torch::Tensor m,
                         torch::Tensor v, c10::optional<torch::Tensor> gdump, torch::Tensor w1bf,
                         c10::optional<torch::Tensor> w1tbf, std::vector<int64_t> off, torch::Tensor adam_t,
-                        int64_t t_off, double lr, double b1, double b2, double eps, double wd, int64_t n_tiles) {
+                        int64_t t_off, double lr, double b1, double b2, double eps, double wd, int64_t n_tiles,
+                        int64_t first_tile) {
   const c10::DeviceGuard g(dc2m.device());
   TORCH_CHECK(mrows == 32 || mrows == 64, "conv2_bwd_fc1: mrows must be 32 or 64");
   TORCH_CHECK(n_tiles >= 0 && n_tiles <= p2cnn::kFc1Tiles, "conv2_bwd_fc1: n_tiles ", n_tiles, " outside [0, ",
               p2cnn::kFc1Tiles, "]");
+  TORCH_CHECK(first_tile >= 0 && first_tile + n_tiles <= p2cnn::kFc1Tiles, "conv2_bwd_fc1: first_tile ", first_tile,
+              " + n_tiles ", n_tiles, " outside [0, ", p2cnn::kFc1Tiles, "]");
   Offsets o = offsets(off);
-  const int64_t n = params_end(o);
-  p2cnn::Fc1Args fc{};
-  fc.dH = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dH, torch::kBFloat16, mrows * 2048, "dH"));
-  fc.a1 = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(a1, torch::kBFloat16, mrows * 3136, "a1"));
-  fc.mrows = int(mrows);
-  fc.params = ptr<float>(params, torch::kFloat32, n, "params");
-  fc.m = ptr<float>(m, torch::kFloat32, n, "m");
-  fc.v = ptr<float>(v, torch::kFloat32, n, "v");
-  fc.gdump = optr<float>(gdump, torch::kFloat32, n, "gdump");
-  fc.w1bf = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1bf, torch::kBFloat16, 2048 * 3136, "w1bf"));
-  fc.w1tbf = reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf"));
-  fc.off = o;
-  fc.adam_t = ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4);
-  fc.t_off = int(t_off);
-  fc.cfg = cfg(lr, b1, b2, eps, wd);
-  return conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, fc, n_tiles);
+  const p2cnn::Fc1Args fc =
+      fc1_args(dH, a1, mrows, params, m, v, gdump, w1bf, w1tbf, o, adam_t, t_off, cfg(lr, b1, b2, eps, wd));
+  return conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, fc, n_tiles, first_tile);
 }
 
 void k_conv_adam(torch::Tensor wslab1, torch::Tensor wslab2, torch::Tensor gb, int64_t B, torch::Tensor params,
@@ -382,8 +425,15 @@ void register_cnn(pybind11::module& m) {
         pybind11::arg("ws") = pybind11::none(), pybind11::arg("ctr") = pybind11::none());
   c.def("fc1_wgrad_adam", &k_fc1_wgrad_adam);
   c.def("conv2_bwd", &k_conv2_bwd);
-  c.def("conv2_bwd_fc1", &k_conv2_bwd_fc1,
-        "conv2_bwd hosting the first n_tiles FC1 weight-gradient + Adam tiles; returns the tiles hosted");
+  namespace py = pybind11;
+  c.def("route_rm_fc1", &k_route_rm_fc1,
+        "the row-major dA1 routing launch hosting FC1 tiles [0, n_tiles), which write w1_write; returns the tiles hosted");
+  c.def("conv2_bwd_fc1", &k_conv2_bwd_fc1, py::arg("dc2m"), py::arg("p1s"), py::arg("am1"), py::arg("w2q"), py::arg("x"),
+        py::arg("idx"), py::arg("wslab1"), py::arg("wslab2"), py::arg("B"), py::arg("dH"), py::arg("a1"), py::arg("mrows"),
+        py::arg("params"), py::arg("m"), py::arg("v"), py::arg("gdump"), py::arg("w1bf"), py::arg("w1tbf"), py::arg("off"),
+        py::arg("adam_t"), py::arg("t_off"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
+        py::arg("n_tiles"), py::arg("first_tile") = 0,
+        "conv2_bwd hosting n_tiles FC1 weight-gradient + Adam tiles from first_tile on; returns the tiles hosted");
   c.def("conv_adam", &k_conv_adam);
   c.def("fc1_conv_adam", &k_fc1_conv_adam, pybind11::arg("dH"), pybind11::arg("a1"), pybind11::arg("mrows"), pybind11::arg("wslab1"),
         pybind11::arg("wslab2"), pybind11::arg("gb"), pybind11::arg("B"), pybind11::arg("params"), pybind11::arg("m"), pybind11::arg("v"), pybind11::arg("gdump"),

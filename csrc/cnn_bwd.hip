@@ -249,16 +249,13 @@ P2_DEVICE float ld_sc1f(const float* p) {
 // slice arrives last) and runs the routing epilogue.  ws: [98][KS][MT*1024] fp32,
 // ctr: [98] int, zero between launches (the last arriver resets its entry).
 template <int MT, int KS>
-__global__ __launch_bounds__(512) void route_rm_kernel(const uint16_t* __restrict__ dH,
-                                                       const uint16_t* __restrict__ w1,
-                                                       const uint8_t* __restrict__ am2, int B,
-                                                       uint16_t* __restrict__ dc2m, float* __restrict__ gb,
-                                                       const float* __restrict__ dlogits,
-                                                       const uint16_t* __restrict__ H, float* __restrict__ p,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       float* __restrict__ gdump, Offsets off,
-                                                       const int* __restrict__ adam_t, int t_off, AdamCfg cfg,
-                                                       float* __restrict__ ws, int* __restrict__ ctr, int xa) {
+P2_DEVICE void route_rm_block(const uint16_t* __restrict__ dH, const uint16_t* __restrict__ w1,
+                              const uint8_t* __restrict__ am2, int B, uint16_t* __restrict__ dc2m,
+                              float* __restrict__ gb, const float* __restrict__ dlogits,
+                              const uint16_t* __restrict__ H, float* __restrict__ p, float* __restrict__ m,
+                              float* __restrict__ v, float* __restrict__ gdump, const Offsets& off,
+                              const int* __restrict__ adam_t, int t_off, const AdamCfg& cfg,
+                              float* __restrict__ ws, int* __restrict__ ctr, int xa) {
   constexpr int NB = kRouteBlocks * KS;
   // xa > 0 (KS = 1): 8 x xa routing blocks, block b on XCD b % 8 takes feature tile
   // (b % 8) xa + b / 8 -- the tiles of FC1 split b % 8, whose W1 columns the skinny
@@ -400,6 +397,20 @@ __global__ __launch_bounds__(512) void route_rm_kernel(const uint16_t* __restric
   }
 }
 
+template <int MT, int KS>
+__global__ __launch_bounds__(512) void route_rm_kernel(const uint16_t* __restrict__ dH,
+                                                       const uint16_t* __restrict__ w1,
+                                                       const uint8_t* __restrict__ am2, int B,
+                                                       uint16_t* __restrict__ dc2m, float* __restrict__ gb,
+                                                       const float* __restrict__ dlogits,
+                                                       const uint16_t* __restrict__ H, float* __restrict__ p,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ gdump, Offsets off,
+                                                       const int* __restrict__ adam_t, int t_off, AdamCfg cfg,
+                                                       float* __restrict__ ws, int* __restrict__ ctr, int xa) {
+  route_rm_block<MT, KS>(dH, w1, am2, B, dc2m, gb, dlogits, H, p, m, v, gdump, off, adam_t, t_off, cfg, ws, ctr, xa);
+}
+
 void route_fc2_rm(const uint16_t* dH, const uint16_t* w1, const uint8_t* am2, int mrows, int B, uint16_t* dc2m,
                   float* gb, const float* dlogits, const uint16_t* H, float* params, float* m, float* v,
                   float* gdump, Offsets off, const int* adam_t, int t_off, AdamCfg cfg, bool with_fc2,
@@ -456,12 +467,35 @@ struct Fc1Lds {
   static constexpr int kBytes = kMain + 128 * 40 * 2;  // + the transposed bf16 tile
 };
 
-template <int MR>
+// The tile's W1 / m / v stream as plain or (NT) non-temporal 16-B accesses.
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+template <bool NT>
+P2_DEVICE float4 fc1_ld4(const float* q) {
+  if constexpr (NT) {
+    const f32x4v t = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(q));
+    return make_float4(t.x, t.y, t.z, t.w);
+  } else {
+    return *reinterpret_cast<const float4*>(q);
+  }
+}
+template <bool NT>
+P2_DEVICE void fc1_st4(float* q, const float4& u) {
+  if constexpr (NT) {
+    f32x4v t = {u.x, u.y, u.z, u.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4v*>(q));
+  } else {
+    *reinterpret_cast<float4*>(q) = u;
+  }
+}
+
+// tid: the thread's index among the tile's 256 (threadIdx.x in a 256-thread launch).
+template <int MR, bool NT = false>
 P2_DEVICE void fc1_wgrad_adam_body(int bx, int by, const uint16_t* __restrict__ dH, const uint16_t* __restrict__ a1,
                                    float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                    float* __restrict__ gdump, uint16_t* __restrict__ w1bf,
                                    uint16_t* __restrict__ w1tbf, const Offsets& off,
-                                   const int* __restrict__ adam_t, int t_off, const AdamCfg& cfg, char* smem) {
+                                   const int* __restrict__ adam_t, int t_off, const AdamCfg& cfg, char* smem,
+                                   int tid) {
   constexpr int AP = Fc1Lds<MR>::AP;
   constexpr int GP = Fc1Lds<MR>::GP;
   uint16_t(*tr)[40] = reinterpret_cast<uint16_t(*)[40]>(smem + Fc1Lds<MR>::kMain);
@@ -472,7 +506,7 @@ P2_DEVICE void fc1_wgrad_adam_body(int bx, int by, const uint16_t* __restrict__ 
   uint16_t* sdh = reinterpret_cast<uint16_t*>(smem);  // [MR][32]  dH[b][n0 + n]
   uint16_t* sa1 = sdh + MR * 32;                      // [MR][AP]  A1[b][kb + k]
   float(*gt)[GP] = reinterpret_cast<float(*)[GP]>(smem);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int n0 = by * 32;
   const int kb = bx * 128;
   // this thread's Adam elements: row nl, k = kb + kq + 32 j + [0, 4)
@@ -486,9 +520,9 @@ P2_DEVICE void fc1_wgrad_adam_body(int bx, int by, const uint16_t* __restrict__ 
     const int k = kb + kq + 32 * j;
     if (k < kFeat) {
       const int64_t e = int64_t(n0 + nl) * kFeat + k;
-      pr[j] = *reinterpret_cast<const float4*>(pw + e);
-      mr[j] = *reinterpret_cast<const float4*>(mw + e);
-      vr[j] = *reinterpret_cast<const float4*>(vw + e);
+      pr[j] = fc1_ld4<NT>(pw + e);
+      mr[j] = fc1_ld4<NT>(mw + e);
+      vr[j] = fc1_ld4<NT>(vw + e);
     }
   }
   for (int i = tid; i < MR * 4; i += 256) {
@@ -549,9 +583,9 @@ P2_DEVICE void fc1_wgrad_adam_body(int bx, int by, const uint16_t* __restrict__ 
     adam_regs(pr[j].y, mr[j].y, vr[j].y, g.y, cfg, s);
     adam_regs(pr[j].z, mr[j].z, vr[j].z, g.z, cfg, s);
     adam_regs(pr[j].w, mr[j].w, vr[j].w, g.w, cfg, s);
-    *reinterpret_cast<float4*>(pw + e) = pr[j];
-    *reinterpret_cast<float4*>(mw + e) = mr[j];
-    *reinterpret_cast<float4*>(vw + e) = vr[j];
+    fc1_st4<NT>(pw + e, pr[j]);
+    fc1_st4<NT>(mw + e, mr[j]);
+    fc1_st4<NT>(vw + e, vr[j]);
     const uint16_t b0 = f32_to_bf16(pr[j].x), b1 = f32_to_bf16(pr[j].y), b2 = f32_to_bf16(pr[j].z),
                    b3 = f32_to_bf16(pr[j].w);
     uint2 o;
@@ -582,7 +616,7 @@ __global__ __launch_bounds__(256) void fc1_wgrad_adam_kernel(const uint16_t* __r
                                                              Offsets off, const int* __restrict__ adam_t, int t_off,
                                                              AdamCfg cfg) {
   __shared__ __attribute__((aligned(16))) char smem[Fc1Lds<MR>::kBytes];
-  fc1_wgrad_adam_body<MR>(blockIdx.x, blockIdx.y, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem);
+  fc1_wgrad_adam_body<MR>(blockIdx.x, blockIdx.y, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem, threadIdx.x);
 }
 
 void fc1_wgrad_adam(const uint16_t* dH, const uint16_t* a1, int mrows, float* params, float* m, float* v,
@@ -595,6 +629,65 @@ void fc1_wgrad_adam(const uint16_t* dH, const uint16_t* a1, int mrows, float* pa
   else
     hipLaunchKernelGGL(fc1_wgrad_adam_kernel<64>, grid, dim3(256), 0, s, dH, a1, params, m, v, gdump, w1bf, w1tbf,
                        off, adam_t, t_off, cfg);
+}
+
+// route_rm_kernel<MT, 1> hosting FC1 weight-gradient + Adam tiles [0, n_fc1): blocks
+// [0, nroute) are the routing (and FC2) blocks of the plain kernel, the blocks behind
+// them run FC1 tiles.  The launch's 128 KB of LDS puts every block alone on a CU, so
+// the hosted blocks land on the CUs the 98 routing blocks leave idle.  The routing
+// blocks read the W1 shadow `w1`; the tiles write the other shadow buffer (f.w1bf_w,
+// checked by the caller), and dH / A1 are only read: no ordering inside the launch.
+// A hosted block runs two tiles, one per 256-thread half, each in its own 64 KB of
+// LDS: both halves pass the same barriers, and a half without a tile (odd n_fc1)
+// leaves before the first one (finished waves do not count at a barrier).  With the
+// 112 routing blocks of the XCD-aligned grid, 144 hosted blocks = 288 tiles give every
+// CU exactly one block; one more block waits for a CU and the launch steps up by
+// 6 us.  The tiles stream W1 / m / v with non-temporal accesses, which leaves the
+// W1 shadow lines of the forward GEMM in L2 for the routing blocks.  Measured
+// (profiles/cnn_route_slice.md, captured step at 288 tiles): one tile per block 73.2,
+// two 69.7, two + non-temporal 68.1 us; non-temporal with one tile per block 73.4.
+template <int MT>
+__global__ __launch_bounds__(512) void route_rm_fc1_kernel(
+    const uint16_t* __restrict__ dH, const uint16_t* __restrict__ w1, const uint8_t* __restrict__ am2, int B,
+    uint16_t* __restrict__ dc2m, float* __restrict__ gb, const float* __restrict__ dlogits,
+    const uint16_t* __restrict__ H, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+    float* __restrict__ gdump, Offsets off, const int* __restrict__ adam_t, int t_off, AdamCfg cfg, int xa, int nroute,
+    Fc1Args f, int n_fc1) {
+  static_assert(2 * Fc1Lds<32 * MT>::kBytes <= kRouteRmLds, "two FC1 tiles fit the launch's dynamic LDS");
+  if (int(blockIdx.x) < nroute) {
+    route_rm_block<MT, 1>(dH, w1, am2, B, dc2m, gb, dlogits, H, p, m, v, gdump, off, adam_t, t_off, cfg, nullptr,
+                          nullptr, xa);
+    return;
+  }
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int kBx = (kFeat + 127) / 128;
+  const int half = threadIdx.x >> 8;
+  const int t = 2 * (int(blockIdx.x) - nroute) + half;
+  if (t >= n_fc1) return;
+  fc1_wgrad_adam_body<32 * MT, true>(t % kBx, t / kBx, f.dH, f.a1, f.params, f.m, f.v, f.gdump, f.w1bf_w, f.w1tbf,
+                                     f.off, f.adam_t, f.t_off, f.cfg, smem + half * (kRouteRmLds / 2),
+                                     threadIdx.x & 255);
+}
+
+int route_rm_fc1(const uint16_t* dH, const uint16_t* w1, const uint8_t* am2, int mrows, int B, uint16_t* dc2m,
+                 float* gb, const float* dlogits, const uint16_t* H, float* params, float* m, float* v, float* gdump,
+                 Offsets off, const int* adam_t, int t_off, AdamCfg cfg, bool with_fc2, const Fc1Args& f, int n_tiles,
+                 hipStream_t s) {
+  if (n_tiles == 0) {
+    route_fc2_rm(dH, w1, am2, mrows, B, dc2m, gb, dlogits, H, params, m, v, gdump, off, adam_t, t_off, cfg, with_fc2,
+                 nullptr, nullptr, s);
+    return 0;
+  }
+  const int xa = xcd_align() ? kRouteBlocks / kXcdSplits : 0;
+  const int nroute = (xa ? 8 * xa : kRouteBlocks) + (with_fc2 ? kFc2Blocks : 0);
+  const dim3 grid(nroute + (n_tiles + 1) / 2);
+  if (mrows == 32)
+    hipLaunchKernelGGL(route_rm_fc1_kernel<1>, grid, dim3(512), kRouteRmLds, s, dH, w1, am2, B, dc2m, gb, dlogits, H,
+                       params, m, v, gdump, off, adam_t, t_off, cfg, xa, nroute, f, n_tiles);
+  else
+    hipLaunchKernelGGL(route_rm_fc1_kernel<2>, grid, dim3(512), kRouteRmLds, s, dH, w1, am2, B, dc2m, gb, dlogits, H,
+                       params, m, v, gdump, off, adam_t, t_off, cfg, xa, nroute, f, n_tiles);
+  return n_tiles;
 }
 
 // ---------------------------------------------------------------------------
@@ -956,10 +1049,11 @@ __global__ __launch_bounds__(256) void conv2_bwd_kernel(const uint16_t* __restri
 }
 
 // conv2_bwd hosting FC1 weight-gradient + Adam tiles: blocks [0, nconv) are the
-// conv roles above, block nconv + f is FC1 tile f (one tile per block, the same
+// conv roles above, block nconv + i is FC1 tile f0 + i (one tile per block, the same
 // body and arithmetic as in fc1_conv_adam_kernel, which then starts at tile
-// gridDim.x - nconv).  The conv blocks fill one CU each (the launch's 143 KB of
-// LDS; a B = 32 launch has 144 of them for 256 CUs), so the dispatcher places the
+// f0 + gridDim.x - nconv; tiles [0, f0) rode in route_rm_fc1_kernel).
+// The conv blocks fill one CU each (the launch's 143 KB of LDS; a B = 32 launch
+// has 144 of them for 256 CUs), so the dispatcher places the
 // FC1 blocks -- higher ids, one per CU as well, the LDS size being the launch's --
 // on the CUs the conv roles leave idle and on those whose dgrad blocks retire
 // first.  Both roles are ready once route_fc2 has finished and neither reads or
@@ -973,7 +1067,7 @@ __global__ __launch_bounds__(256) void conv2_bwd_fc1_kernel(
     const uint16_t* __restrict__ dc2m, const uint16_t* __restrict__ p1s, const uint8_t* __restrict__ am1,
     const uint16_t* __restrict__ w2q, const uint8_t* __restrict__ xds, const int64_t* __restrict__ idx,
     float* __restrict__ wslab1, float* __restrict__ wslab2, int B, int nconv, int wg_blocks, int stream_w,
-    int wg_first, Fc1Args f) {
+    int wg_first, Fc1Args f, int f0) {
   static_assert(Fc1Lds<MR>::kBytes <= kDgLds, "the launch's dynamic LDS serves the FC1 role too");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int kBx = (kFeat + 127) / 128;
@@ -982,14 +1076,14 @@ __global__ __launch_bounds__(256) void conv2_bwd_fc1_kernel(
     conv2_bwd_roles(j, nconv, dc2m, p1s, am1, w2q, xds, idx, wslab1, wslab2, B, wg_blocks, stream_w, wg_first, smem);
     return;
   }
-  const int t = j - nconv;
-  fc1_wgrad_adam_body<MR>(t % kBx, t / kBx, f.dH, f.a1, f.params, f.m, f.v, f.gdump, f.w1bf, f.w1tbf, f.off, f.adam_t,
-                          f.t_off, f.cfg, smem);
+  const int t = j - nconv + f0;
+  fc1_wgrad_adam_body<MR>(t % kBx, t / kBx, f.dH, f.a1, f.params, f.m, f.v, f.gdump, f.w1bf_w, f.w1tbf, f.off, f.adam_t,
+                          f.t_off, f.cfg, smem, threadIdx.x);
 }
 
 int conv2_bwd_fc1(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
                   const int64_t* idx, float* wslab1, float* wslab2, int B, const Fc1Args& f, int n_tiles,
-                  hipStream_t s) {
+                  int first_tile, hipStream_t s) {
   // P2CNN_CONV2BWD_ROLES (measurement knob, read once): 1 = dgrad blocks
   // only, 2 = wgrad blocks only; unset = both (the product).  Measured
   // (scripts/kbench.py, B = 32): dgrad 7.3 us, wgrad 13.1 us, both 12.5 us.
@@ -1029,16 +1123,16 @@ int conv2_bwd_fc1(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1,
                        wslab2, B, first, wg_blocks, stream_w, roles == 3 ? wg_first : 0);
   else if (f.mrows == 32)
     hipLaunchKernelGGL(conv2_bwd_fc1_kernel<32>, dim3(blocks + na), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx,
-                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f);
+                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f, first_tile);
   else
     hipLaunchKernelGGL(conv2_bwd_fc1_kernel<64>, dim3(blocks + na), dim3(256), kDgLds, s, dc2m, p1s, am1, w2q, x, idx,
-                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f);
+                       wslab1, wslab2, B, blocks, wg_blocks, stream_w, wg_first, f, first_tile);
   return na;
 }
 
 void conv2_bwd(const uint16_t* dc2m, const uint16_t* p1s, const uint8_t* am1, const uint16_t* w2q, const uint8_t* x,
                const int64_t* idx, float* wslab1, float* wslab2, int B, hipStream_t s) {
-  conv2_bwd_fc1(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, Fc1Args{}, 0, s);
+  conv2_bwd_fc1(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, Fc1Args{}, 0, 0, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1243,7 +1337,7 @@ __global__ __launch_bounds__(256) void fc1_conv_adam_kernel(
     return;
   }
   const int f = j - kCA + f0;  // tiles [0, f0) ran in conv2_bwd_fc1
-  fc1_wgrad_adam_body<MR>(f % kBx, f / kBx, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem);
+  fc1_wgrad_adam_body<MR>(f % kBx, f / kBx, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem, threadIdx.x);
 }
 
 void fc1_conv_adam(const uint16_t* dH, const uint16_t* a1, int mrows, const float* wslab1, const float* wslab2,
@@ -1326,7 +1420,7 @@ __global__ __launch_bounds__(256) void fc1_conv_adam_fwd_kernel(
   j -= kCA;
   constexpr int nfc1 = kBx * (kHid / 32);
   if (j < nfc1) {
-    fc1_wgrad_adam_body<MR>(j % kBx, j / kBx, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem);
+    fc1_wgrad_adam_body<MR>(j % kBx, j / kBx, dH, a1, p, m, v, gdump, w1bf, w1tbf, off, adam_t, t_off, cfg, smem, threadIdx.x);
     return;
   }
   j -= nfc1;
@@ -1398,6 +1492,10 @@ void init_attributes() {
                                hipFuncAttributeMaxDynamicSharedMemorySize, kRouteRmLds / 2));
   P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(route_rm_kernel<2, 2>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, kRouteRmLds / 2));
+  P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(route_rm_fc1_kernel<1>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kRouteRmLds));
+  P2_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(route_rm_fc1_kernel<2>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kRouteRmLds));
 }
 
 }  // namespace p2cnn

@@ -76,9 +76,17 @@ _FWD_IN_ADAM = os.environ.get("P2PFL_CNN_FWD_IN_ADAM", "0") == "1"
 # FC1 weight-gradient + Adam tiles (of 1600) hosted by the conv2 backward launch, on
 # the CUs its 144 one-per-CU workgroups leave idle; the FC1 Adam launch starts at that
 # tile (csrc/cnn_bwd.hip conv2_bwd_fc1_kernel; profiles/cnn_fc1_slice.md).  0: the
-# plain conv2_bwd and the whole stream in fc1_conv_adam.
-FC1_SLICE_DEFAULT = 384
+# plain conv2_bwd and the whole stream in fc1_conv_adam.  (384 before the routing launch
+# hosted tiles too; with the Adam launch shorter the optimum moved, profiles/cnn_route_slice.md.)
+FC1_SLICE_DEFAULT = 448
 FC1_TILES = 1600
+# FC1 tiles hosted by the dA1 routing launch, on the 158 CUs its 98 one-per-CU
+# workgroups leave idle (csrc/cnn_bwd.hip route_rm_fc1_kernel; profiles/cnn_route_slice.md).
+# Routing reads the row-major W1 shadow the tiles rewrite, so such a step reads one of two
+# shadow buffers and writes the other ("hops"); the conv2 backward launch then hosts the
+# next fc1_slice tiles.  288 tiles are 144 two-tile workgroups: with the 112 routing
+# workgroups exactly one per CU.  0: no hopping, the plain routing launch.
+ROUTE_SLICE_DEFAULT = 288
 _NAMES = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "l1.weight", "l1.bias", "l2.weight", "l2.bias")
 FEAT, HID = 3136, 2048
 
@@ -98,6 +106,7 @@ class FusedCNNEngine:
         arena: Optional[ModuleArena] = None,
         split_fc1: Optional[int] = None,
         fc1_slice: Optional[int] = None,
+        route_slice: Optional[int] = None,
     ) -> None:
         self.C = ops.ext().cnn
         self.C.init()
@@ -123,6 +132,13 @@ class FusedCNNEngine:
         self.fc1_slice = int(fc1_slice if fc1_slice is not None else os.environ.get("P2PFL_CNN_FC1_SLICE", FC1_SLICE_DEFAULT))
         if not 0 <= self.fc1_slice <= FC1_TILES:
             raise ValueError(f"FC1 slice {self.fc1_slice} outside [0, {FC1_TILES}]")
+        # FC1 tiles hosted by the dA1 routing launch on the default step (P2PFL_CNN_ROUTE_SLICE);
+        # the built-in default gives way to a large fc1_slice, an explicit value must fit beside it
+        room = FC1_TILES - self.fc1_slice
+        rs = route_slice if route_slice is not None else os.environ.get("P2PFL_CNN_ROUTE_SLICE")
+        self.route_slice = int(rs) if rs is not None else min(ROUTE_SLICE_DEFAULT, room)
+        if not 0 <= self.route_slice <= room:
+            raise ValueError(f"route slice {self.route_slice} outside [0, {room}] (1600 - fc1_slice)")
         dev, bf = self.device, torch.bfloat16
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
         n = self.arena.flat.numel()
@@ -136,7 +152,14 @@ class FusedCNNEngine:
         # bf16 weight shadows in kernel-friendly layouts
         self.w2r, self.w2q = z(51200, dt=bf), z(51200, dt=bf)
         self.route_rm = _ROUTE_RM
+        # row-major W1 shadow: two buffers on the arm whose routing launch can host FC1
+        # tiles (a hopping step reads one and writes the other).  OUTSIDE an enqueued plan
+        # the current shadow is buffer 0, w1bf: pack_shadows, the evaluation snapshots and
+        # captured graphs (which replay from a fixed start) rely on it.
         self.w1bf = z(HID * FEAT, dt=bf)
+        self._hop_arm = _MERGED_ADAM and self.route_rm and not _ROUTE_SPLIT and not _FWD_IN_ADAM
+        self._w1s = (self.w1bf, z(HID * FEAT, dt=bf) if self._hop_arm else None)
+        self._wp = 0
         self.w1tbf = None if self.route_rm else z(HID * FEAT, dt=bf)
         # bf16 FC2 weight read by the head (half the bytes of the fp32 master per
         # head workgroup); refreshed by the merged Adam launch's FC2 blocks, so only
@@ -178,9 +201,26 @@ class FusedCNNEngine:
         return self.arena.flat
 
     @property
+    def w1_cur(self) -> torch.Tensor:
+        """The current row-major W1 shadow (buffer 0 outside an enqueued plan)."""
+        return self._w1s[self._wp]
+
+    @property
     def w1_route(self) -> torch.Tensor:
         """The W1 operand of the dA1 routing kernel (row-major W1, or the W1^T shadow)."""
-        return self.w1bf if self.route_rm else self.w1tbf
+        return self.w1_cur if self.route_rm else self.w1tbf
+
+    def hop_steps(self, steps: int) -> int:
+        """How many of a plan's ``steps`` hop between the W1 shadow buffers: an even count
+        of leading steps, so the plan ends on buffer 0 (an odd last step runs in place)."""
+        return steps - steps % 2 if self._hop_arm and self.route_slice else 0
+
+    def settle_shadow(self) -> None:
+        """Make buffer 0 the current W1 shadow again after a plan was left early."""
+        if self._wp:
+            if not torch.cuda.is_current_stream_capturing():  # an abandoned capture ran nothing
+                self.w1bf.copy_(self._w1s[1])
+            self._wp = 0
 
     def pack_shadows(self) -> None:
         """Refresh the bf16 weight copies after the fp32 parameters changed externally."""
@@ -206,13 +246,13 @@ class FusedCNNEngine:
         else:
             C.conv1_fwd(x, idx, self.params, self.off, self.p1, self.am1, self.p1s if train else None, B)
             C.conv2_fwd(self.p1, self.w2r, self.params, self.off, self.a1, self.am2, B, M)
-        C.gemm_skinny(self.a1, self.w1bf, self.slabs1, M, HID, FEAT, self.S1)
+        C.gemm_skinny(self.a1, self.w1_cur, self.slabs1, M, HID, FEAT, self.S1)
         C.head(self.slabs1, self.S1, M, self.params, self.off, labels, idx, B, train, self.H, self.dH, self.dlogits, stats,
                self.w2bf)
 
     def train_step_async(
         self, x: torch.Tensor, labels: torch.Tensor, idx: Optional[torch.Tensor], B: int, stats: torch.Tensor, t_off: int,
-        nxt: Optional[Tuple[Optional[torch.Tensor], int]] = None, fwd_done: bool = False,
+        nxt: Optional[Tuple[Optional[torch.Tensor], int]] = None, fwd_done: bool = False, hop: bool = False,
     ) -> None:
         """Enqueue one training step (no host sync; graph-capturable).
 
@@ -245,11 +285,41 @@ class FusedCNNEngine:
         one workgroup per CU; bitwise-equal results for every slice.  The
         opt-in arms below (next forward inside the Adam launch, separate Adam
         launches) keep the plain conv2_bwd.
+        The dA1 routing launch hosts FC1 tiles as well (``hop``, ``route_rm_fc1``): its
+        98 workgroups take a CU each (128 KB of LDS) for ~8 us and leave 158 idle.
+        Routing reads the row-major W1 shadow the tiles rewrite, so the engine keeps
+        two shadow buffers and a hopping step reads one (forward GEMM, routing) while
+        every FC1 tile of the step -- in whichever launch -- writes the other; the
+        fp32 W1 / m / v stay in place (tiles are disjoint).  A plan hops an even
+        number of leading steps (``hop_steps``) and runs an odd last step in place, so
+        outside a plan the current shadow is always buffer 0, ``w1bf``.  A hosted
+        workgroup runs two tiles, one per 256-thread half, with non-temporal W1 / m / v
+        accesses: ``route_slice`` = 288 tiles (one workgroup on every CU), then
+        ``fc1_slice`` = 448 in conv2_bwd: routing 8.0 -> 9.2 us, the Adam launch
+        23.3 -> 17.6 us, the captured step 72.0 -> 68.4 us (profiles/cnn_route_slice.md);
+        bitwise-equal results.  In-place steps host nothing in the routing launch.
         """
         if B > self.mrows:
             raise ValueError(f"batch {B} > engine capacity {self.mrows}")
+        if hop and not (self._hop_arm and nxt is None and not fwd_done):
+            raise ValueError("only the default step can hop between the W1 shadow buffers")
         C, M, a = self.C, self.mrows, self._adam()
         self.forward(x, labels, idx, B, stats, True, convs=not fwd_done)
+        if hop:
+            # the forward and the routing read the current W1 shadow, every FC1 tile of the
+            # step writes the other buffer: the routing launch can host tiles [0, route_slice)
+            w1r, w1w = self.w1_cur, self._w1s[1 - self._wp]
+            nr = C.route_rm_fc1(self.dH, w1r, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H, self.params,
+                                self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, False, self.a1, w1w,
+                                self.route_slice)
+            na = nr + C.conv2_bwd_fc1(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B,
+                                      self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, w1w, None,
+                                      self.off, self.adam_t, t_off, *a, self.fc1_slice, nr)
+            C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
+                            self.gdump, w1w, None, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
+                            self.dlogits, self.H, self.w2bf, na)
+            self._wp ^= 1
+            return
         if _MERGED_ADAM:
             # dA1 routing alone, the conv backward, then ONE launch for the
             # FC2 and conv-parameter Adam (latency-bound) and the FC1 wgrad +
@@ -261,10 +331,10 @@ class FusedCNNEngine:
                 # the conv backward hosts the first FC1 tiles; the Adam launch takes the rest
                 # (not on the next-forward-in-Adam arm, whose steps pass nxt or fwd_done)
                 na = C.conv2_bwd_fc1(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B,
-                                     self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1bf,
+                                     self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1_cur,
                                      self.w1tbf, self.off, self.adam_t, t_off, *a, self.fc1_slice)
                 C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
-                                self.gdump, self.w1bf, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
+                                self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
                                 self.dlogits, self.H, self.w2bf, na)
                 return
             C.conv2_bwd(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B)
@@ -273,19 +343,19 @@ class FusedCNNEngine:
                 # same launch; the next step then passes fwd_done
                 idx_n, Bn = nxt
                 C.fc1_conv_adam_fwd(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m,
-                                    self.v, self.gdump, self.w1bf, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t,
+                                    self.v, self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t,
                                     t_off, *a, self.dlogits, self.H, self.w2bf, x, idx_n, self.p1, self.am1, self.p1s,
                                     self._a1s[1 - self._par], self.am2, Bn, self._fwd_sync)
                 self._par ^= 1
                 return
             C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
-                            self.gdump, self.w1bf, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
+                            self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
                             self.dlogits, self.H, self.w2bf)
             return
         C.route_fc2(self.dH, self.w1_route, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H,
                     self.params, self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, True, self.route_rm,
                     self.route_ws, self.route_ctr)
-        C.fc1_wgrad_adam(self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1bf, self.w1tbf, self.off, self.adam_t, t_off, *a)
+        C.fc1_wgrad_adam(self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1_cur, self.w1tbf, self.off, self.adam_t, t_off, *a)
         C.conv2_bwd(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B)
         C.conv_adam(self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v, self.gdump, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a)
 
@@ -509,17 +579,23 @@ class FusedCNNLearner(TorchLearner):
         chain = train and _FWD_IN_ADAM and _MERGED_ADAM and self.engine.mrows <= 64
         if train:
             self.engine._par = 0  # the captured sequence of A1 parities starts here on every replay
-        for j, (s, b) in enumerate(plan):
-            idx = perm[s : s + b]
-            st = stats[j] if train else stats[0]
-            if train:
-                nxt = None
-                if chain and j + 1 < len(plan):
-                    s2, b2 = plan[j + 1]
-                    nxt = (perm[s2 : s2 + b2], b2)
-                self.engine.train_step_async(x, y, idx, b, st, j + 1, nxt=nxt, fwd_done=chain and j > 0)
-            else:
-                self._eval_fwd.forward(x, y, idx, b, st, snap)
+        # the leading even number of training steps hops between the W1 shadow buffers, so the
+        # plan starts and ends on buffer 0 (an odd last step runs in place)
+        hops = self.engine.hop_steps(len(plan)) if train else 0
+        try:
+            for j, (s, b) in enumerate(plan):
+                idx = perm[s : s + b]
+                st = stats[j] if train else stats[0]
+                if train:
+                    nxt = None
+                    if chain and j + 1 < len(plan):
+                        s2, b2 = plan[j + 1]
+                        nxt = (perm[s2 : s2 + b2], b2)
+                    self.engine.train_step_async(x, y, idx, b, st, j + 1, nxt=nxt, fwd_done=chain and j > 0, hop=j < hops)
+                else:
+                    self._eval_fwd.forward(x, y, idx, b, st, snap)
+        finally:
+            self.engine.settle_shadow()  # a plan left early (an error mid-way) ends on buffer 0 too
 
     def _capture(self, name, loader, plan, train, key) -> _EpochGraph:
         n = len(loader.dataset)

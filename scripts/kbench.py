@@ -11,6 +11,13 @@ run directly or under ``rocprofv3 --pmc ... -- python3 scripts/kbench.py``.
 the first ``n`` FC1 tiles (``conv2_bwd_fc1``), the merged Adam launch from tile ``n``
 (``fc2_fc1_conv_adam``), their sum, and the graph-captured step of an engine with
 ``fc1_slice = n`` (``step_graph``; the figure the default is picked from).
+
+``--route-slice 0,128,256`` adds, per routing slice ``r`` (and per ``--fc1-slice`` value
+``n``, default the engine's): the routing launch hosting FC1 tiles ``[0, r)``
+(``route_rm_fc1``), the conv2 backward launch hosting ``[r, r + n)``, the merged Adam
+launch from tile ``r + n``, their sum (``trio``), and the graph-captured step of an engine
+with ``route_slice = r, fc1_slice = n``: 20 steps, an even count, so every step hops
+between the two W1 shadow buffers.
 """
 
 from __future__ import annotations
@@ -32,6 +39,7 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--no-graph", action="store_true", help="skip the graph-captured step (use under --pmc)")
     ap.add_argument("--fc1-slice", default="", help="comma-separated FC1 slices to sweep (see above)")
+    ap.add_argument("--route-slice", default="", help="comma-separated routing-launch slices to sweep (see above)")
     args = ap.parse_args()
 
     from p2pfl_amd.learning.fused_cnn import FusedCNNEngine
@@ -90,13 +98,15 @@ def main() -> None:
         """One step of ``eng`` as it is configured now: 20 captured, 5 replays."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
+        hop = eng.hop_steps(20) == 20  # an even plan: every step hops when the routing launch hosts tiles
         with torch.cuda.stream(s):
-            eng.train_step_async(x, y, None, B, stats, 1)
+            for _ in range(2):
+                eng.train_step_async(x, y, None, B, stats, 1, hop=hop)
         torch.cuda.current_stream().wait_stream(s)
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr):
             for _ in range(20):
-                eng.train_step_async(x, y, None, B, stats, 1)
+                eng.train_step_async(x, y, None, B, stats, 1, hop=hop)
         gr.replay()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -116,7 +126,27 @@ def main() -> None:
     if not only and not args.no_graph:
         res["step_graph"] = step_graph()
     slices = {}
-    for n in [int(v) for v in args.fc1_slice.split(",") if v]:
+    fc1_slices = [int(v) for v in args.fc1_slice.split(",") if v]
+    route_slices = [int(v) for v in args.route_slice.split(",") if v]
+    routes = {}
+    for n in (fc1_slices or [eng.fc1_slice]) if route_slices else []:
+        for r in route_slices:
+            if r + n > 1600:
+                continue
+            w1w = eng._w1s[1]  # the hosted tiles write the shadow buffer the routing blocks do not read
+            t = {
+                "route_rm_fc1": timeit(lambda: C.route_rm_fc1(eng.dH, eng.w1bf, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, False, eng.a1, w1w, r)),
+                "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, w1w, None, eng.off, eng.adam_t, 1, *a, n, r)),
+                "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, w1w, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, r + n)),
+            }
+            t["trio"] = round(sum(t.values()), 2)
+            if not args.no_graph:
+                keep = eng.fc1_slice, eng.route_slice
+                eng.fc1_slice, eng.route_slice = n, r
+                t["step_graph"] = step_graph()
+                eng.fc1_slice, eng.route_slice = keep
+            routes[f"{r}+{n}"] = t
+    for n in [] if route_slices else fc1_slices:
         r = {
             "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a, n)),
             "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, n)),
@@ -132,6 +162,8 @@ def main() -> None:
     out = {"us_per_kernel": res, "batch": B}
     if slices:
         out["fc1_slice"] = slices
+    if routes:
+        out["route+fc1_slice"] = routes
     print(json.dumps(out))
 
 

@@ -6,6 +6,7 @@
 #include <c10/core/DeviceGuard.h>
 
 #include <cmath>
+#include <cstdint>
 #include <vector>
 
 #include "kernels.h"
@@ -103,6 +104,112 @@ torch::Tensor pairwise_sqdist(std::vector<torch::Tensor> srcs) {
   torch::Tensor out = torch::empty({k, k}, opts);
   p2::pairwise_sqdist(a.ptrs.data(), a.bf.data(), k, partials.data_ptr<float>(), out.data_ptr<float>(), a.n, stream());
   return out;
+}
+
+// ---- block-quantised int8 wire (quant_wire.hip) ------------------------------
+int64_t q8_packed_nbytes(int64_t n, int64_t n_raw) {
+  TORCH_CHECK(n >= 1 && n_raw >= 0, "q8: n must be >= 1 and n_raw >= 0");
+  const int64_t nb = (n + 63) / 64;
+  return 64 * nb + 256 * n_raw + 4 * nb;
+}
+
+// The raw-block table: int32, on the arena's device, sorted, unique, below nb.
+// The kernels index the arena with these values, so they are checked on the
+// host before anything is launched.  Two forms:
+//  * Q8RawTable: built from host integers, checked once where it is built, then
+//    copied to the device and never handed out again except as a copy -- what
+//    the kernels read is what was checked, and a call costs no read-back
+//    (p2pfl_amd.learning.arena.q8_raw_table makes these);
+//  * any int32 device tensor: read back and checked on every call, which waits
+//    for the work queued on the current stream.
+struct Q8RawTable {
+  torch::Tensor ids;  // int32 [R] on the device
+  int64_t last;       // largest index: good for every nb above it
+};
+Q8RawTable make_raw_table(const std::vector<int64_t>& blocks, int64_t device) {
+  TORCH_CHECK(!blocks.empty(), "Q8RawTable: no blocks");
+  torch::Tensor host = torch::empty({int64_t(blocks.size())}, torch::dtype(torch::kInt32));
+  int32_t* h = host.data_ptr<int32_t>();
+  int64_t prev = -1;
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    TORCH_CHECK(blocks[i] >= 0 && blocks[i] <= INT32_MAX, "Q8RawTable: block index ", blocks[i], " is out of range");
+    TORCH_CHECK(blocks[i] > prev, "Q8RawTable: blocks must be sorted and unique");
+    prev = blocks[i];
+    h[i] = int32_t(prev);
+  }
+  return Q8RawTable{host.to(torch::Device(torch::kCUDA, c10::DeviceIndex(device))), prev};
+}
+
+struct RawIds {
+  const int32_t* ptr = nullptr;
+  int R = 0;
+};
+RawIds check_raw_ids(const pybind11::object& raw_obj, int64_t nb, const torch::Device& dev, const char* op) {
+  RawIds r;
+  if (raw_obj.is_none()) return r;
+  if (pybind11::isinstance<Q8RawTable>(raw_obj)) {
+    const Q8RawTable& t = raw_obj.cast<const Q8RawTable&>();  // lives as long as the caller's argument
+    TORCH_CHECK(t.ids.device() == dev, op, ": raw_blocks must be on the arena's device");
+    TORCH_CHECK(t.last < nb, op, ": raw block index ", t.last, " is outside [0, ", nb, ")");
+    r.ptr = t.ids.data_ptr<int32_t>();
+    r.R = int(t.ids.numel());
+    return r;
+  }
+  const torch::Tensor raw_t = raw_obj.cast<torch::Tensor>();
+  const torch::Tensor* raw = &raw_t;
+  if (!raw->defined() || raw->numel() == 0) return r;
+  TORCH_CHECK(raw->scalar_type() == torch::kInt32 && raw->dim() == 1 && raw->is_contiguous(), op,
+              ": raw_blocks must be a contiguous 1-D int32 tensor");
+  TORCH_CHECK(raw->device() == dev, op, ": raw_blocks must be on the arena's device");
+  TORCH_CHECK(raw->numel() <= nb, op, ": more raw blocks than blocks");
+  // (this read waits for the work queued on the current stream: the price of
+  // checking the indices a kernel is about to use, every time)
+  const torch::Tensor host = raw->cpu();
+  const int32_t* h = host.data_ptr<int32_t>();
+  int64_t prev = -1;
+  for (int64_t i = 0; i < host.numel(); ++i) {
+    TORCH_CHECK(h[i] >= 0 && h[i] < nb, op, ": raw block index ", h[i], " is outside [0, ", nb, ")");
+    TORCH_CHECK(h[i] > prev, op, ": raw_blocks must be sorted and unique");
+    prev = h[i];
+  }
+  r.ptr = raw->data_ptr<int32_t>();
+  r.R = int(raw->numel());
+  return r;
+}
+
+void check_packed(const torch::Tensor& packed, int64_t n, int R, const torch::Device& dev, const char* op) {
+  TORCH_CHECK(packed.is_cuda() && packed.device() == dev, op, ": packed must be a GPU tensor on the arena's device");
+  TORCH_CHECK(packed.scalar_type() == torch::kUInt8 && packed.dim() == 1 && packed.is_contiguous(), op,
+              ": packed must be a contiguous 1-D uint8 tensor");
+  TORCH_CHECK(packed.numel() == q8_packed_nbytes(n, R), op, ": packed holds ", packed.numel(), " bytes, expected ",
+              q8_packed_nbytes(n, R), " for ", n, " elements and ", R, " raw blocks");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0, op, ": packed must be 16-byte aligned");
+}
+
+torch::Tensor q8_encode(torch::Tensor src, pybind11::object raw_blocks, c10::optional<torch::Tensor> out) {
+  check_arena(src, "src");
+  TORCH_CHECK(src.dim() == 1 && src.numel() >= 1, "q8_encode: src must be a 1-D arena of at least one element");
+  const int64_t n = src.numel();
+  const RawIds raw = check_raw_ids(raw_blocks, (n + 63) / 64, src.device(), "q8_encode");
+  const c10::DeviceGuard guard(src.device());
+  torch::Tensor packed = (out.has_value() && out->defined())
+                             ? *out
+                             : torch::empty({q8_packed_nbytes(n, raw.R)},
+                                            torch::TensorOptions().dtype(torch::kUInt8).device(src.device()));
+  check_packed(packed, n, raw.R, src.device(), "q8_encode");
+  p2::q8_encode(src.data_ptr(), src.scalar_type() == torch::kBFloat16 ? 1 : 0, n, raw.ptr, raw.R,
+                packed.data_ptr<uint8_t>(), stream());
+  return packed;
+}
+
+void q8_decode(torch::Tensor packed, int64_t n, pybind11::object raw_blocks, torch::Tensor out) {
+  check_arena(out, "out");
+  TORCH_CHECK(n >= 1 && out.dim() == 1 && out.numel() == n, "q8_decode: out must be a 1-D arena of n elements");
+  const RawIds raw = check_raw_ids(raw_blocks, (n + 63) / 64, out.device(), "q8_decode");
+  check_packed(packed, n, raw.R, out.device(), "q8_decode");
+  const c10::DeviceGuard guard(out.device());
+  p2::q8_decode(packed.data_ptr<uint8_t>(), n, raw.ptr, raw.R, out.data_ptr(),
+                out.scalar_type() == torch::kBFloat16 ? 1 : 0, stream());
 }
 
 uint16_t* opt_bf16(const c10::optional<torch::Tensor>& t, int64_t n) {
@@ -296,6 +403,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pairwise_sqdist", &pairwise_sqdist,
         "k x k fp32 matrix of squared L2 distances between 2..16 arenas, one pass, deterministic",
         pybind11::arg("srcs"));
+  m.def("q8_packed_nbytes", &q8_packed_nbytes, "bytes of the q8 packed buffer of n elements with n_raw raw blocks",
+        pybind11::arg("n"), pybind11::arg("n_raw") = 0);
+  pybind11::class_<Q8RawTable>(m, "Q8RawTable", "a q8 raw-block table checked where it is built (sorted, unique)")
+      .def(pybind11::init(&make_raw_table), pybind11::arg("blocks"), pybind11::arg("device") = 0)
+      .def("__len__", [](const Q8RawTable& t) { return t.ids.numel(); })
+      .def("tensor", [](const Q8RawTable& t) { return t.ids.clone(); }, "a copy of the device table");
+  m.def("q8_encode", &q8_encode,
+        "block-quantise a flat fp32/bf16 arena: int8 codes + one fp32 scale per 64 elements, raw blocks kept in fp32",
+        pybind11::arg("src"), pybind11::arg("raw_blocks") = pybind11::none(), pybind11::arg("out") = pybind11::none());
+  m.def("q8_decode", &q8_decode, "decode a q8 packed buffer of n elements into a flat fp32/bf16 arena",
+        pybind11::arg("packed"), pybind11::arg("n"), pybind11::arg("raw_blocks"), pybind11::arg("out"));
   m.def("adam_step", &adam_step, "fused whole-arena Adam/AdamW step");
   m.def("sgd_step", &sgd_step, "fused whole-arena SGD(+momentum/nesterov) step");
   m.def("adam_mt_step", &adam_mt_step, "multi-tensor Adam/AdamW over per-tensor grads into flat fp32 state",

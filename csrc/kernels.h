@@ -35,6 +35,19 @@ int pairwise_sqdist_blocks(int64_t n);
 void pairwise_sqdist(const void* const* srcs, const int* src_bf16, int k, float* partials, float* out, int64_t n,
                      hipStream_t s);
 
+// Block-quantised int8 wire (quant_wire.hip).  packed: 64 nb int8 codes, then
+// the 256 R bytes of the R raw blocks as fp32, then nb fp32 scales, nb =
+// ceil(n / 64); 16-byte aligned.  raw_ids: device table of R sorted, unique
+// block indices below nb (may be null when R = 0).  Encode: per block scale =
+// amax / 127, code = clamp(rint(x / scale), -127, 127); a block holding NaN or
+// Inf gets a NaN scale, one below 127 FLT_MIN a zero scale (codes 0 in both).
+// Decode: float(code) * scale, then the raw blocks exactly.  Any n >= 1; src /
+// out fp32 or bf16.  Both throw std::invalid_argument for n < 1 or R < 0.
+void q8_encode(const void* src, int src_bf16, int64_t n, const int32_t* raw_ids, int R, uint8_t* packed,
+               hipStream_t s);
+void q8_decode(const uint8_t* packed, int64_t n, const int32_t* raw_ids, int R, void* out, int out_bf16,
+               hipStream_t s);
+
 struct AdamParams {
   float lr, beta1, beta2, eps, weight_decay;
   float step_size;     // lr / (1 - beta1^t)

@@ -43,6 +43,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="aggregation strategy of every node (trimmed_mean: trim=1, krum: f=1, m=1)")
     p.add_argument("--device", default=None, help="cpu / cuda / cuda:N (default: GPU if present)")
     p.add_argument("--fast", action="store_true", help="shrink gossip/heartbeat periods (test settings)")
+    p.add_argument("--wire_dtype", choices=["fp32", "bf16", "q8"], default=None,
+                   help="element type of models on the wire (sets Settings.WIRE_DTYPE; default: leave it as it is, "
+                        "fp32 unless the caller changed it): bf16 applies to the xGMI data "
+                        "plane only, q8 (int8 codes + one scale per 64 elements) to every serialising transport")
     # reference flag names (p2pfl/examples/mnist.py:44-66)
     p.add_argument("--use_unix_socket", action="store_true", help="gRPC over unix domain sockets")
     p.add_argument("--use_local_protocol", action="store_true", help="in-memory transport (= --protocol memory)")
@@ -107,6 +111,8 @@ def main(argv=None) -> None:
         set_test_settings()
     else:
         Settings.LOG_LEVEL = "INFO"
+    if args.wire_dtype is not None:
+        Settings.WIRE_DTYPE = args.wire_dtype
     mnist(args.nodes, args.rounds, args.epochs, args.show_metrics, args.measure_time, args.model, args.protocol,
           args.partition, args.alpha, args.batch, args.device, args.use_unix_socket, args.aggregator)
 

@@ -61,6 +61,22 @@ class ParamLayout:
             out.append(n)
         return tuple(out)
 
+    def well_formed(self) -> bool:
+        """What :meth:`from_tensors` guarantees, checked for a layout that came
+        from a peer (:meth:`from_json` checks nothing): one entry per tensor in
+        every field, no negative dimension, every tensor on an ``ALIGN``
+        boundary, after the (padded) end of the one before it and inside
+        ``numel``.  Arithmetic only: nothing is sized by the layout's numbers."""
+        k = len(self.names)
+        if not (len(self.shapes) == len(self.dtypes) == len(self.offsets) == k) or self.numel < 1:
+            return False
+        end = 0
+        for shape, off, n in zip(self.shapes, self.offsets, self.sizes()):
+            if any(d < 0 for d in shape) or off < end or off % ALIGN or off + n > self.numel:
+                return False
+            end = _align(off + n)
+        return True
+
     def compatible(self, other: "ParamLayout") -> bool:
         return self.shapes == other.shapes and self.offsets == other.offsets and self.numel == other.numel
 
@@ -82,6 +98,94 @@ class ParamLayout:
             tuple(int(o) for o in d["offsets"]),
             int(d["numel"]),
         )
+
+
+# q8 wire: which 64-element blocks travel as exact fp32.  A layout is frozen, so
+# the answer is cached beside it (by value: equal layouts share one entry), with
+# one int32 device table per device for the kernels.  Layouts also arrive from
+# peers, so both caches are small LRUs: a node sees its own model's layout and
+# little else.
+_Q8_CACHE = 8
+_Q8_RAW: "OrderedDict[ParamLayout, Tuple[int, ...]]" = OrderedDict()
+_Q8_RAW_TABLES: "OrderedDict[Tuple[ParamLayout, torch.device], Any]" = OrderedDict()
+
+
+def _lru_get(cache: "OrderedDict", key: Any) -> Any:
+    try:
+        cache.move_to_end(key)
+        return cache[key]
+    except KeyError:  # also a concurrent eviction
+        return None
+
+
+def _lru_put(cache: "OrderedDict", key: Any, value: Any) -> None:
+    cache[key] = value
+    while len(cache) > _Q8_CACHE:
+        try:
+            cache.popitem(last=False)
+        except KeyError:
+            break
+
+
+def q8_raw_count(layout: ParamLayout) -> int:
+    """``len(q8_raw_blocks(layout))`` by arithmetic, without building the list:
+    what a receiver checks a header and a body size against before it expands
+    anything from a layout a peer sent.  ValueError if the layout is not
+    :meth:`~ParamLayout.well_formed` (its tensors could then share blocks)."""
+    if not layout.well_formed():
+        raise ValueError("malformed parameter layout")
+    return sum((n + ALIGN - 1) // ALIGN for shape, n in zip(layout.shapes, layout.sizes()) if len(shape) <= 1)
+
+
+def q8_raw_blocks(layout: ParamLayout) -> Tuple[int, ...]:
+    """Sorted indices of the 64-element blocks that the ``"q8"`` wire carries
+    exactly: every block of every tensor whose shape has at most one dimension
+    (biases, LayerNorm / BatchNorm scale and shift, ``running_mean``,
+    ``running_var``, ``num_batches_tracked``).  An 8-bit linear code can decode
+    a small BatchNorm variance as 0, and ``rsqrt(0 + eps)`` then blows the
+    activation up.  Sender and receiver both derive the list from the layout
+    with this function; the wire header carries only its length.
+
+    The list has up to ``numel / 64`` entries.  For a layout that came off the
+    wire, first hold :func:`q8_raw_count` and ``numel`` against the bytes that
+    actually arrived (``wire.decode_params`` and the xGMI receiver do).
+    ValueError if the layout is not well formed."""
+    blocks = _lru_get(_Q8_RAW, layout)
+    if blocks is None:
+        if not layout.well_formed():
+            raise ValueError("malformed parameter layout")
+        out = []
+        for shape, off, n in zip(layout.shapes, layout.offsets, layout.sizes()):
+            if len(shape) <= 1:
+                # tensors start on a block boundary (ALIGN) and never share a block
+                out.extend(range(off // ALIGN, (off + n + ALIGN - 1) // ALIGN))
+        blocks = tuple(out)  # ascending: a well-formed layout's tensors are in offset order
+        _lru_put(_Q8_RAW, layout, blocks)
+    return blocks
+
+
+def q8_raw_table(layout: ParamLayout, device: Any) -> Any:
+    """:func:`q8_raw_blocks` as the table ``ops.q8_encode`` / ``ops.q8_decode`` take
+    on ``device`` (None if there are none): an int32 tensor on the CPU; on a GPU
+    the extension's ``Q8RawTable``, which is checked once here, where it is
+    built, so that a call does not have to read the table back."""
+    blocks = q8_raw_blocks(layout)
+    if not blocks:
+        return None
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (layout, device)
+    t = _lru_get(_Q8_RAW_TABLES, key)
+    if t is None:
+        if device.type == "cuda":
+            from p2pfl_amd import ops
+
+            t = ops.ext().Q8RawTable(list(blocks), device.index)
+        else:
+            t = torch.tensor(blocks, dtype=torch.int32)
+        _lru_put(_Q8_RAW_TABLES, key, t)
+    return t
 
 
 class FlatParams(OrderedDict):

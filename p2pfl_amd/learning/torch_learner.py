@@ -338,7 +338,7 @@ class TorchLearner(NodeLearner):
             if isinstance(data, FlatParams):
                 params = data.to(self.device, non_blocking=True)
             elif isinstance(data, (bytes, bytearray, memoryview)):
-                params = decode_params(data)
+                params = decode_params(data, device=self.device)  # a q8 arena is unpacked on the device
                 if isinstance(params, FlatParams):
                     params = params.to(self.device)
             else:

@@ -25,8 +25,12 @@ by its pickle protocol header.
 
 Header: ``{"kind": "flat", "layout": ParamLayout}`` for arena payloads (one
 contiguous fp32 block -- one device-to-host copy to encode, one host-to-device
-copy to decode), or ``{"kind": "dict", "tensors": [[name, dtype, shape,
-offset, nbytes], ...]}`` for arbitrary tensor dicts.
+copy to decode); with ``Settings.WIRE_DTYPE == "q8"`` the same header plus
+``"enc": "q8", "block": 64, "raw": R`` over the block-quantised arena
+(``ops.q8_encode``: int8 codes, ``R`` exact fp32 blocks, one fp32 scale per 64
+elements; 0.27 of the fp32 bytes, packed and unpacked on the arena's device);
+or ``{"kind": "dict", "tensors": [[name, dtype, shape, offset, nbytes], ...]}``
+for arbitrary tensor dicts.
 """
 
 from __future__ import annotations
@@ -41,7 +45,7 @@ from typing import Mapping, Union
 import numpy as np
 import torch
 
-from p2pfl_amd.learning.arena import FlatParams, ParamLayout
+from p2pfl_amd.learning.arena import FlatParams, ParamLayout, q8_raw_count, q8_raw_table
 from p2pfl_amd.learning.exceptions import DecodingParamsError
 
 MAGIC = b"P2FA"
@@ -204,7 +208,18 @@ def encode_params(params: Mapping[str, torch.Tensor]) -> bytes:
 
         return encode_reference_payload(params)
     if isinstance(params, FlatParams):
-        return _pack({"kind": "flat", "layout": params.layout.to_json()}, _tensor_bytes(params.flat[: params.layout.numel]))
+        layout = params.layout
+        flat = params.flat[: layout.numel]
+        if Settings.WIRE_DTYPE == "q8":
+            # packed on the arena's own device: the device-to-host copy and the
+            # CRC then cover 1.06 n bytes instead of 4 n
+            from p2pfl_amd import ops
+
+            packed = ops.q8_encode(flat.detach(), q8_raw_table(layout, flat.device))
+            header = {"kind": "flat", "layout": layout.to_json(), "enc": "q8", "block": ops.Q8_BLOCK,
+                      "raw": q8_raw_count(layout)}
+            return _pack(header, _tensor_bytes(packed))
+        return _pack({"kind": "flat", "layout": layout.to_json()}, _tensor_bytes(flat))
     entries, blobs, off = [], [], 0
     for name, t in params.items():
         b = _tensor_bytes(t)
@@ -214,9 +229,40 @@ def encode_params(params: Mapping[str, torch.Tensor]) -> bytes:
     return _pack({"kind": "dict", "tensors": entries}, b"".join(blobs))
 
 
-def decode_params(data: Union[bytes, bytearray, memoryview]) -> Union[FlatParams, "OrderedDict[str, torch.Tensor]", list]:
+def _decode_q8(header: dict, body: memoryview, layout: ParamLayout, device) -> FlatParams:
+    """A q8 arena payload.  The layout comes from the peer like the body, so it
+    is only trusted as far as the bytes that arrived vouch for it: it must be
+    well formed, and the packed size it implies -- worked out by arithmetic,
+    nothing is built from the layout's numbers yet -- must be the body's
+    length.  Only then is the raw-block list expanded (it is then no longer
+    than the body) and a byte of the body interpreted."""
+    from p2pfl_amd import ops
+
+    if header.get("block") != ops.Q8_BLOCK:
+        raise DecodingParamsError(f"unsupported q8 block size {header.get('block')!r}")
+    if not layout.well_formed():
+        raise DecodingParamsError("malformed parameter layout")
+    n_raw = q8_raw_count(layout)
+    if header.get("raw") != n_raw:
+        raise DecodingParamsError(f"q8 payload lists {header.get('raw')!r} raw blocks, the layout has {n_raw}")
+    if len(body) != ops.q8_packed_nbytes(layout.numel, n_raw):
+        raise DecodingParamsError("truncated or oversized q8 payload")
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    packed = torch.from_numpy(np.frombuffer(body, dtype=np.uint8).copy()).to(dev)  # one host-to-device copy
+    flat = ops.q8_decode(packed, layout.numel, q8_raw_table(layout, dev))
+    return FlatParams.from_flat(flat, layout)
+
+
+def decode_params(
+    data: Union[bytes, bytearray, memoryview], device=None
+) -> Union[FlatParams, "OrderedDict[str, torch.Tensor]", list]:
     """Decode a payload: this codec's frame, or (a list of tensors) the
-    reference's pickled ``[ndarray, ...]`` read by the allow-listed decoder."""
+    reference's pickled ``[ndarray, ...]`` read by the allow-listed decoder.
+
+    A frame is decoded by what its header says, whatever this node's own
+    ``Settings.WIRE_DTYPE``.  ``device``: where a quantised (``"enc": "q8"``)
+    arena is unpacked -- the packed bytes are copied there and decoded by the
+    kernel; None = on the CPU.  Every other payload comes back on the CPU."""
     from p2pfl_amd.learning import refpickle
 
     if refpickle.looks_like_pickle(data):
@@ -227,6 +273,11 @@ def decode_params(data: Union[bytes, bytearray, memoryview]) -> Union[FlatParams
         header = json.loads(hbytes.decode())
         if header["kind"] == "flat":
             layout = ParamLayout.from_json(header["layout"])
+            enc = header.get("enc")
+            if enc == "q8":
+                return _decode_q8(header, body, layout, device)
+            if enc is not None:
+                raise DecodingParamsError(f"unknown arena encoding {enc!r}")
             if len(body) != layout.numel * 4:
                 raise DecodingParamsError("truncated flat payload")
             arr = np.frombuffer(body, dtype="<f4")

@@ -253,6 +253,171 @@ def pairwise_sqdist(flats: Sequence[torch.Tensor]) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------
+# block-quantised int8 model wire, "q8" (csrc/quant_wire.hip)
+# ----------------------------------------------------------------------------
+Q8_BLOCK = 64  # elements per quantisation block = arena.ALIGN: a block never mixes two tensors
+_Q8_NAN_BITS = 0x7FC00000
+_Q8_INF_BITS = 0x7F800000
+_Q8_TINY = 127.0 * 2.0**-126  # 127 * FLT_MIN, exact in fp32
+
+
+def q8_packed_nbytes(n: int, n_raw: int = 0) -> int:
+    """Bytes of the packed buffer of ``n`` elements with ``n_raw`` raw blocks:
+    ``64 nb`` int8 codes, ``256 n_raw`` bytes of exact fp32 blocks, ``4 nb``
+    bytes of fp32 scales, ``nb = ceil(n / 64)``; every section 64-byte aligned."""
+    n, n_raw = int(n), int(n_raw)
+    if n < 1 or n_raw < 0:
+        raise ValueError("q8: n must be >= 1 and n_raw >= 0")
+    nb = -(-n // Q8_BLOCK)
+    return 64 * nb + 256 * n_raw + 4 * nb
+
+
+def _q8_raw_ids(raw_blocks, nb: int, device: torch.device, table_ok: bool = False):
+    """``raw_blocks`` as what the kernels or the reference take on ``device``: an
+    int32 tensor, or (``table_ok``: for the kernels) the extension's
+    ``Q8RawTable`` unchanged (None when there are none).  Checked here for host tables; the bindings check device tables."""
+    if raw_blocks is None:
+        return None
+    if type(raw_blocks).__name__ == "Q8RawTable":  # the extension's table, checked where it was built
+        if table_ok:
+            return raw_blocks
+        raw_blocks = raw_blocks.tensor().cpu()
+    t = raw_blocks if isinstance(raw_blocks, torch.Tensor) else torch.tensor(list(raw_blocks), dtype=torch.int32)
+    if t.numel() == 0:
+        return None
+    if t.dtype != torch.int32 or t.dim() != 1:
+        raise ValueError("q8: raw_blocks must be a 1-D int32 tensor")
+    if not t.is_cuda:
+        if int(t.min()) < 0 or int(t.max()) >= nb:
+            raise ValueError(f"q8: raw block index outside [0, {nb})")
+        if t.numel() > 1 and not bool((t[1:] > t[:-1]).all()):
+            raise ValueError("q8: raw_blocks must be sorted and unique")
+    return t.to(device).contiguous()
+
+
+def q8_encode_reference(flat: torch.Tensor, raw_blocks=None) -> torch.Tensor:
+    """The q8 format written out literally in torch (IEEE binary32 throughout):
+    per 64-element block ``scale = amax / 127`` and ``code = clamp(rint(x /
+    scale), -127, 127)``; a block holding NaN or Inf gets a quiet-NaN scale and
+    one with ``amax < 127 FLT_MIN`` a zero scale, codes 0 in both; the blocks
+    in ``raw_blocks`` are also carried as exact fp32."""
+    x = flat.detach().reshape(-1).float()  # bf16 widens exactly
+    n = x.numel()
+    nb = -(-n // Q8_BLOCK)
+    raw = _q8_raw_ids(raw_blocks, nb, x.device)
+    n_raw = 0 if raw is None else raw.numel()
+    xb = torch.zeros(nb * Q8_BLOCK, dtype=torch.float32, device=x.device)
+    xb[:n] = x
+    xb = xb.view(nb, Q8_BLOCK)
+    # the unsigned order of |x| bit patterns is their numeric order, and every
+    # Inf / NaN pattern is >= 0x7F800000 (int32 is enough: the sign bit is cleared)
+    mbits = (xb.view(torch.int32) & 0x7FFFFFFF).max(dim=1).values.contiguous()
+    amax = mbits.view(torch.float32)
+    nonfinite = mbits >= _Q8_INF_BITS
+    tiny = ~nonfinite & (amax < _Q8_TINY)
+    normal = ~(nonfinite | tiny)
+    scale = amax / 127.0
+    q = torch.round(xb / torch.where(normal, scale, torch.ones_like(scale))[:, None]).clamp_(-127.0, 127.0)
+    q = torch.where(normal[:, None], q, torch.zeros_like(q)).to(torch.int8)
+    sbits = scale.view(torch.int32).clone()
+    sbits[tiny] = 0
+    sbits[nonfinite] = _Q8_NAN_BITS
+    packed = torch.empty(q8_packed_nbytes(n, n_raw), dtype=torch.uint8, device=x.device)
+    c, r = 64 * nb, 256 * n_raw
+    packed[:c] = q.view(torch.uint8).reshape(-1)
+    if n_raw:
+        packed[c : c + r] = xb[raw.long()].contiguous().view(torch.uint8).reshape(-1)
+    packed[c + r :] = sbits.view(torch.uint8).reshape(-1)
+    return packed
+
+
+def _q8_cast(y: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """fp32 -> ``out_dtype``, round-to-nearest-even.  Rounding says nothing about
+    a NaN, and torch's CPU conversion answers differently from one machine to
+    the next (0x7FC0 on its scalar path, 0xFFFF on its AVX-512 one), so the
+    format pins the usual IEEE choice, which is also what the gfx950 conversion
+    instruction does: a bf16 NaN keeps the sign and the upper payload bits of
+    the fp32 NaN and has its quiet bit set."""
+    out = y.to(out_dtype)
+    if out_dtype == torch.bfloat16:
+        nan = torch.isnan(y)
+        if bool(nan.any()):
+            bits = (y.contiguous().view(torch.int32) >> 16) | 0x40  # arithmetic shift: the int16 pattern, sign kept
+            out.view(torch.int16)[nan] = bits[nan].to(torch.int16)
+    return out
+
+
+def q8_decode_reference(packed: torch.Tensor, n: int, raw_blocks=None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``y = float(code) * scale`` (one fp32 multiply), converted to ``out_dtype``
+    round-to-nearest-even (:func:`_q8_cast`), then the raw blocks overwritten
+    with their exact values."""
+    n = int(n)
+    nb = -(-n // Q8_BLOCK)
+    raw = _q8_raw_ids(raw_blocks, nb, packed.device)
+    n_raw = 0 if raw is None else raw.numel()
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or packed.numel() != q8_packed_nbytes(n, n_raw):
+        raise ValueError("q8_decode: packed buffer does not have the size of n elements and these raw blocks")
+    c, r = 64 * nb, 256 * n_raw
+    codes = packed[:c].clone().view(torch.int8).view(nb, Q8_BLOCK)
+    scales = packed[c + r :].clone().view(torch.float32)
+    y = _q8_cast(codes.float() * scales[:, None], out_dtype)
+    if n_raw:
+        y[raw.long()] = _q8_cast(packed[c : c + r].clone().view(torch.float32).view(n_raw, Q8_BLOCK), out_dtype)
+    return y.reshape(-1)[:n].clone()
+
+
+def q8_encode(flat: torch.Tensor, raw_blocks=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pack a flat fp32 / bf16 arena into the q8 wire format: a ``uint8`` tensor
+    of :func:`q8_packed_nbytes` bytes on the arena's device (0.27 of the fp32
+    bytes).  ``raw_blocks``: sorted, unique int32 block indices kept exactly
+    (:func:`p2pfl_amd.learning.arena.q8_raw_blocks`), already on the arena's
+    device.  One kernel on the GPU plus a small one for the raw blocks.  A
+    raw-block table given as a device tensor is read back and checked by the
+    extension on every call, which waits for the work queued on the current
+    stream; the ``Q8RawTable`` that ``q8_raw_table`` makes was checked where it
+    was built and costs nothing per call."""
+    flat = flat.detach().reshape(-1)
+    if not _gpu(flat):
+        res = q8_encode_reference(flat, raw_blocks)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    if flat.dtype not in (torch.float32, torch.bfloat16):
+        flat = flat.float()
+    if not (flat.is_contiguous() and flat.data_ptr() % 16 == 0):
+        flat = flat.clone(memory_format=torch.contiguous_format)  # a fresh, aligned block
+    nb = -(-flat.numel() // Q8_BLOCK)
+    return ext().q8_encode(flat, _q8_raw_ids(raw_blocks, nb, flat.device, table_ok=True), out)
+
+
+def q8_decode(
+    packed: torch.Tensor,
+    n: int,
+    raw_blocks=None,
+    out: Optional[torch.Tensor] = None,
+    out_dtype: torch.dtype = torch.float32,
+) -> torch.Tensor:
+    """Unpack a q8 buffer of ``n`` elements into a flat fp32 (default) or bf16
+    arena on the buffer's device; ``raw_blocks`` as for :func:`q8_encode`."""
+    n = int(n)
+    if out is not None:
+        out_dtype = out.dtype
+    if not _gpu(packed):
+        res = q8_decode_reference(packed, n, raw_blocks, out_dtype)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    if not (packed.is_contiguous() and packed.data_ptr() % 16 == 0):
+        packed = packed.clone(memory_format=torch.contiguous_format)
+    if out is None:
+        out = torch.empty(n, dtype=out_dtype, device=packed.device)
+    ext().q8_decode(packed, n, _q8_raw_ids(raw_blocks, -(-n // Q8_BLOCK), packed.device, table_ok=True), out)
+    return out
+
+
+# ----------------------------------------------------------------------------
 # optimizers (whole-arena, in place)
 # ----------------------------------------------------------------------------
 def adam_step_reference(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, decoupled=False):

@@ -108,9 +108,16 @@ class Settings:
     ``pickle.dumps([ndarray, ...])``, to federate with stock p2pfl peers; it is
     always *read* with an allow-listed non-executing decoder)."""
     WIRE_DTYPE: str = "fp32"
-    """Element type of model arenas on the xGMI data plane: ``"fp32"`` (the
-    reference's numerics) or ``"bf16"`` (half the bytes per link; receivers
-    average bf16 inputs in fp32)."""
+    """Element type of model arenas on the wire: ``"fp32"`` (the reference's
+    numerics), ``"bf16"`` (half the bytes per link; receivers average bf16
+    inputs in fp32) or ``"q8"`` (int8 codes with one fp32 scale per 64-element
+    block, tensors of at most one dimension kept in exact fp32: 0.27 of the
+    fp32 bytes; receivers unpack to fp32 on arrival).  ``"bf16"`` applies to
+    the xGMI data plane only -- gRPC and the bus fallback then send fp32.
+    ``"q8"`` applies to every transport that serialises weights: the xGMI data
+    plane, gRPC and the bus fallback (``WIRE_FORMAT == "p2fa"``; the in-memory
+    transport passes arenas by reference and has no wire).  A receiver decodes
+    whatever encoding arrives, whatever its own setting."""
     TORCH_NUM_THREADS: int | None = None
     """If set, ``torch.set_num_threads`` value used by the learners
     (the reference hard-codes 1: ``lightning_learner.py:38``)."""

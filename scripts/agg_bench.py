@@ -11,6 +11,7 @@ back-to-back calls, every arm warmed up and timed for >= --seconds in total:
     torch_sqdist  (a - b).square().sum() per pair
 
     python scripts/agg_bench.py [--seconds 0.3] [--rounds 5] [--out table.md]
+    python scripts/agg_bench.py --q8 ...    the q8 wire kernels beside the k = 1 weighted sum (q8_main)
 
 Prints one JSON line per point and a markdown table (time per call in us,
 min..max over the rounds as the spread, achieved GB/s by the byte counts above).
@@ -57,8 +58,76 @@ def torch_sqdist(flats):
     return d
 
 
+def q8_main(args) -> None:
+    """--q8: the q8 wire kernels beside the k = 1 weighted sum, at the arenas of
+    the MNIST CNN and of ResNet-50 with their own raw-block tables.
+
+        q8_encode     fp32 arena -> packed             4n + packed bytes
+        q8_decode     packed -> fp32 arena             packed + 4n bytes
+        wsum_k1       ops.weighted_average([x], [1])   8n bytes
+        q8_*_r0       the same without raw blocks: the main launch alone
+    """
+    from p2pfl_amd import ops
+    from p2pfl_amd.learning.arena import flatten, q8_raw_blocks, q8_raw_table
+    from p2pfl_amd.models import CNN
+    from p2pfl_amd.models.resnet import ResNet50
+
+    rows = []
+    for name, make in (("cnn", CNN), ("resnet50", ResNet50)):
+        layout = flatten(make().state_dict()).layout
+        n, raw = layout.numel, q8_raw_table(layout, "cuda")
+        n_raw = len(q8_raw_blocks(layout))
+        nbytes = ops.q8_packed_nbytes(n, n_raw)
+        x = torch.randn(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+        out = torch.empty(n, device="cuda")
+        packed = ops.q8_encode(x, raw)
+        packed0 = ops.q8_encode(x)  # no raw blocks: the main launch alone
+        arms = {
+            "q8_encode": (lambda: ops.q8_encode(x, raw, out=packed), 4 * n + nbytes),
+            "q8_decode": (lambda: ops.q8_decode(packed, n, raw, out=out), nbytes + 4 * n),
+            "wsum_k1": (lambda: ops.weighted_average([x], [1.0], out=out), 8 * n),
+            "q8_encode_r0": (lambda: ops.q8_encode(x, out=packed0), 4 * n + packed0.numel()),
+            "q8_decode_r0": (lambda: ops.q8_decode(packed0, n, out=out), packed0.numel() + 4 * n),
+        }
+        reps = {}
+        for arm, (fn, _) in arms.items():
+            fn()
+            torch.cuda.synchronize()
+            reps[arm] = max(1, math.ceil(args.seconds * 1e6 / args.rounds / batch_us(fn, 2)))
+        samples = {arm: [] for arm in arms}
+        for _ in range(args.rounds):
+            for arm, (fn, _) in arms.items():
+                samples[arm].append(batch_us(fn, reps[arm]))
+        point = {"size": name, "n": n, "raw_blocks": n_raw, "packed_bytes": nbytes}
+        for arm, (_, moved) in arms.items():
+            s = sorted(samples[arm])
+            med = s[len(s) // 2]
+            point[arm] = {"us": round(med, 1), "min_us": round(s[0], 1), "max_us": round(s[-1], 1),
+                          "GBps": round(moved / med / 1e3, 1), "calls": reps[arm] * args.rounds}
+        print(json.dumps(point), flush=True)
+        rows.append(point)
+        del x, out, packed, packed0
+        torch.cuda.empty_cache()
+    arms = ["q8_encode", "q8_decode", "wsum_k1", "q8_encode_r0", "q8_decode_r0"]
+    lines = ["| arena | raw blocks | packed / fp32 bytes | " + " | ".join(f"{a} us (min..max) / GB/s" for a in arms)
+             + " | encode / wsum | decode / wsum |", "|---|---|---|" + "---|" * (len(arms) + 2)]
+    for p in rows:
+        cells = [f"{p[a]['us']} ({p[a]['min_us']}..{p[a]['max_us']}) / {p[a]['GBps']}" for a in arms]
+        lines.append(f"| {p['size']} ({p['n']}) | {p['raw_blocks']} | {p['packed_bytes'] / (4 * p['n']):.4f} | "
+                     + " | ".join(cells) + f" | {p['q8_encode']['us'] / p['wsum_k1']['us']:.2f} | "
+                     f"{p['q8_decode']['us'] / p['wsum_k1']['us']:.2f} |")
+    table = "\n".join(lines)
+    print(table)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(table + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--q8", action="store_true",
+                    help="time ops.q8_encode / ops.q8_decode beside the k = 1 weighted sum instead (CNN and ResNet-50 arenas)")
     ap.add_argument("--seconds", type=float, default=0.3, help="timed work per arm and point, at least")
     ap.add_argument("--rounds", type=int, default=5, help="alternations of the arms (spread = min..max over them)")
     ap.add_argument("--sizes", default="cnn,vit_b")
@@ -69,6 +138,8 @@ def main() -> None:
     from p2pfl_amd import ops
 
     ops.ext()
+    if args.q8:
+        return q8_main(args)
     rows = []
     for name in args.sizes.split(","):
         n = SIZES[name]

@@ -40,6 +40,9 @@ def main() -> None:
     ap.add_argument("--learner", choices=["fused", "torch"], default="fused")
     ap.add_argument("--watchdog", type=float, default=600)
     ap.add_argument("--log-level", default="WARNING", help="node log level (INFO shows every stage / gossip step)")
+    ap.add_argument("--dp-clip", type=float, default=None,
+                    help="give every node a GaussianMechanism with this clip norm (default: none, updates leave as they are)")
+    ap.add_argument("--dp-noise", type=float, default=0.0, help="its noise multiplier (with --dp-clip)")
     args = ap.parse_args()
     import faulthandler
 
@@ -63,7 +66,12 @@ def main() -> None:
     nodes = []
     for i in range(args.peers):
         data = MnistFederatedDM(sub_id=i % args.number_sub, number_sub=args.number_sub)
-        n = Node(CNN(seed=i), data, learner=L, protocol=InMemoryCommunicationProtocol, device=dev)
+        privacy = None
+        if args.dp_clip is not None:
+            from p2pfl_amd.learning.privacy import GaussianMechanism
+
+            privacy = GaussianMechanism(args.dp_clip, args.dp_noise, seed=i)
+        n = Node(CNN(seed=i), data, learner=L, protocol=InMemoryCommunicationProtocol, device=dev, privacy=privacy)
         n.start()
         nodes.append(n)
     try:
@@ -100,6 +108,7 @@ def main() -> None:
                 "samples_per_sec_per_peer": round(n_train * args.epochs / steady, 1),
                 "final_test_accuracy": acc,
                 "learner": args.learner,
+                "privacy": None if args.dp_clip is None else {"clip_norm": args.dp_clip, "noise_multiplier": args.dp_noise},
                 "device": str(dev),
                 "config": "MNIST-CNN, batch 32, Adam 1e-3, 2700-sample shards, in-memory transport (device payloads), 1 GPU",
             }

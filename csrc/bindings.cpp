@@ -212,6 +212,59 @@ void q8_decode(torch::Tensor packed, int64_t n, pybind11::object raw_blocks, tor
                 out.scalar_type() == torch::kBFloat16 ? 1 : 0, stream());
 }
 
+// ---- differentially private updates (dp_update.hip) --------------------------
+// w / w0 / out: fp32 arenas of one size (a multiple of 64) on one device; table:
+// uint8 [n / 64] on that device (its values are only compared against, so they
+// need no check).
+int64_t check_dp(const torch::Tensor& w, const torch::Tensor& w0, const torch::Tensor& table, const char* op) {
+  check_f32(w, "w");
+  check_f32(w0, "w0");
+  const int64_t n = w.numel();
+  TORCH_CHECK(w.dim() == 1 && n >= 64 && n % 64 == 0, op, ": w must be a 1-D arena of a positive multiple of 64 elements");
+  TORCH_CHECK(w0.dim() == 1 && w0.numel() == n && w0.device() == w.device(), op, ": w0 must have w's size and device");
+  TORCH_CHECK(table.is_cuda() && table.device() == w.device() && table.scalar_type() == torch::kUInt8 &&
+                  table.dim() == 1 && table.is_contiguous() && table.numel() == n / 64,
+              op, ": table must be a contiguous uint8 [n / 64] tensor on the arena's device");
+  return n;
+}
+
+bool overlaps(const torch::Tensor& a, const torch::Tensor& b) {
+  const auto a0 = reinterpret_cast<uintptr_t>(a.data_ptr()), b0 = reinterpret_cast<uintptr_t>(b.data_ptr());
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+
+torch::Tensor dp_delta_sqnorm(torch::Tensor w, torch::Tensor w0, torch::Tensor table) {
+  const int64_t n = check_dp(w, w0, table, "dp_delta_sqnorm");
+  const c10::DeviceGuard guard(w.device());
+  const auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(w.device());
+  torch::Tensor partials = torch::empty({int64_t(p2::dp_sqnorm_blocks(n))}, opts);
+  torch::Tensor out = torch::empty({1}, opts);
+  p2::dp_delta_sqnorm(w.data_ptr<float>(), w0.data_ptr<float>(), table.data_ptr<uint8_t>(), n,
+                      partials.data_ptr<float>(), out.data_ptr<float>(), stream());
+  return out;
+}
+
+torch::Tensor dp_apply(torch::Tensor w, torch::Tensor w0, torch::Tensor table, torch::Tensor sqnorm, double clip,
+                       double noise_multiplier, uint64_t seed, int64_t round, c10::optional<torch::Tensor> out) {
+  const int64_t n = check_dp(w, w0, table, "dp_apply");
+  TORCH_CHECK(sqnorm.is_cuda() && sqnorm.device() == w.device() && sqnorm.scalar_type() == torch::kFloat32 &&
+                  sqnorm.numel() == 1,
+              "dp_apply: sqnorm must be a 1-element float32 tensor on the arena's device");
+  const float c = float(clip), sigma = float(noise_multiplier * clip);  // the product rounded once
+  TORCH_CHECK(std::isfinite(c) && c > 0.f, "dp_apply: clip must be finite and > 0");
+  TORCH_CHECK(std::isfinite(sigma) && noise_multiplier >= 0.0, "dp_apply: noise_multiplier must be finite and >= 0");
+  TORCH_CHECK(noise_multiplier == 0.0 || sigma > 0.f, "dp_apply: noise_multiplier * clip underflows float32");
+  TORCH_CHECK(round >= 0 && round <= int64_t(UINT32_MAX), "dp_apply: round must be in [0, 2^32)");
+  const c10::DeviceGuard guard(w.device());
+  torch::Tensor o = (out.has_value() && out->defined()) ? *out : torch::empty_like(w);
+  check_f32(o, "out");
+  TORCH_CHECK(o.dim() == 1 && o.numel() == n && o.device() == w.device(), "dp_apply: out must have w's size and device");
+  TORCH_CHECK(!overlaps(o, w) && !overlaps(o, w0), "dp_apply: out must not overlap w or w0");
+  p2::dp_apply(w.data_ptr<float>(), w0.data_ptr<float>(), table.data_ptr<uint8_t>(), sqnorm.data_ptr<float>(), c,
+               sigma, seed, uint32_t(round), o.data_ptr<float>(), n, stream());
+  return o;
+}
+
 uint16_t* opt_bf16(const c10::optional<torch::Tensor>& t, int64_t n) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 && t->is_contiguous() && t->numel() >= n,
@@ -414,6 +467,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("src"), pybind11::arg("raw_blocks") = pybind11::none(), pybind11::arg("out") = pybind11::none());
   m.def("q8_decode", &q8_decode, "decode a q8 packed buffer of n elements into a flat fp32/bf16 arena",
         pybind11::arg("packed"), pybind11::arg("n"), pybind11::arg("raw_blocks"), pybind11::arg("out"));
+  m.def("dp_delta_sqnorm", &dp_delta_sqnorm,
+        "1-element fp32 tensor: sum (w - w0)^2 over the elements the block table privatises, deterministic",
+        pybind11::arg("w"), pybind11::arg("w0"), pybind11::arg("table"));
+  m.def("dp_apply", &dp_apply,
+        "clip the update w - w0 to L2 norm clip (given its squared norm) and add N(0, (noise_multiplier clip)^2) "
+        "to the privatised elements; a fresh arena, everything else copied from w",
+        pybind11::arg("w"), pybind11::arg("w0"), pybind11::arg("table"), pybind11::arg("sqnorm"), pybind11::arg("clip"),
+        pybind11::arg("noise_multiplier"), pybind11::arg("seed"), pybind11::arg("round"),
+        pybind11::arg("out") = pybind11::none());
   m.def("adam_step", &adam_step, "fused whole-arena Adam/AdamW step");
   m.def("sgd_step", &sgd_step, "fused whole-arena SGD(+momentum/nesterov) step");
   m.def("adam_mt_step", &adam_mt_step, "multi-tensor Adam/AdamW over per-tensor grads into flat fp32 state",

@@ -48,6 +48,27 @@ void q8_encode(const void* src, int src_bf16, int64_t n, const int32_t* raw_ids,
 void q8_decode(const uint8_t* packed, int64_t n, const int32_t* raw_ids, int R, void* out, int out_bf16,
                hipStream_t s);
 
+// Differentially private updates (dp_update.hip): the Gaussian mechanism on
+// delta = w - w0.  w, w0, out: fp32 arenas of n elements, n a positive multiple
+// of 64, 16-byte aligned; table: n / 64 bytes, byte c = the first c elements of
+// that 64-element block are privatised, the rest copied through (0: an exempt
+// block).  Both throw std::invalid_argument for any other n.
+//
+// out[0] = sum (w[i] - w0[i])^2 over the privatised elements, fp32.  partials:
+// dp_sqnorm_blocks(n) floats of workspace.  Fixed-order reductions, no atomics,
+// a grid that depends on n alone: the same inputs give the bitwise-same sum.
+int dp_sqnorm_blocks(int64_t n);
+void dp_delta_sqnorm(const float* w, const float* w0, const uint8_t* table, int64_t n, float* partials, float* out,
+                     hipStream_t s);
+// Privatised elements: out = base + sigma * g, base = w if *sqnorm <= clip^2
+// (bitwise) else w0 + (clip / sqrt(*sqnorm)) * (w - w0), every operation singly
+// rounded; g: Philox4x32-10 (key = seed, counter = (i / 4, round)) through
+// Box-Muller, |g| <= 5.77, a function of (seed, round, i) alone.  sigma = 0
+// launches a kernel without any noise code.  Everything else: out = w bitwise.
+// out must not overlap w or w0.  Throws unless clip > 0 and sigma >= 0.
+void dp_apply(const float* w, const float* w0, const uint8_t* table, const float* sqnorm, float clip, float sigma,
+              uint64_t seed, uint32_t round, float* out, int64_t n, hipStream_t s);
+
 struct AdamParams {
   float lr, beta1, beta2, eps, weight_decay;
   float step_size;     // lr / (1 - beta1^t)

@@ -2,7 +2,8 @@
 
 Reference: p2pfl/examples/mnist.py (same flags: --nodes --rounds --epochs
 --show_metrics --measure_time), plus --model, --protocol, --partition,
---device and --aggregator (fedavg, or a Byzantine-robust one).  Data is
+--device, --aggregator (fedavg, or a Byzantine-robust one) and --dp_clip /
+--dp_noise (differentially private updates).  Data is
 synthetic MNIST-shaped unless P2PFL_MNIST_DIR points at the IDX files.
 Metrics are printed as a table (no plotting dependency).
 """
@@ -12,12 +13,13 @@ from __future__ import annotations
 import argparse
 import os
 import time
-from typing import List
+from typing import List, Optional
 
 from p2pfl_amd.communication.grpc import GrpcCommunicationProtocol
 from p2pfl_amd.communication.memory import InMemoryCommunicationProtocol
 from p2pfl_amd.data import MnistFederatedDM
 from p2pfl_amd.learning.aggregators import FedAvg, FedMedian, Krum, TrimmedMean
+from p2pfl_amd.learning.privacy import GaussianMechanism
 from p2pfl_amd.management.logger import logger
 from p2pfl_amd.models import CNN, MLP
 from p2pfl_amd.node import Node
@@ -47,11 +49,19 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="element type of models on the wire (sets Settings.WIRE_DTYPE; default: leave it as it is, "
                         "fp32 unless the caller changed it): bf16 applies to the xGMI data "
                         "plane only, q8 (int8 codes + one scale per 64 elements) to every serialising transport")
+    p.add_argument("--dp_clip", type=float, default=None,
+                   help="differentially private updates: every node clips its round's update to this L2 norm before "
+                        "releasing it (learning.privacy.GaussianMechanism; default: off)")
+    p.add_argument("--dp_noise", type=float, default=0.0,
+                   help="noise multiplier z of --dp_clip C: N(0, (z C)^2) is added to every released coordinate "
+                        "(0: clipping only, no privacy guarantee)")
     # reference flag names (p2pfl/examples/mnist.py:44-66)
     p.add_argument("--use_unix_socket", action="store_true", help="gRPC over unix domain sockets")
     p.add_argument("--use_local_protocol", action="store_true", help="in-memory transport (= --protocol memory)")
     p.add_argument("--token", type=str, default="", help="API token for the web logger (http://localhost:3000)")
     args = p.parse_args(argv)
+    if args.dp_clip is None and args.dp_noise:
+        p.error("--dp_noise needs --dp_clip.")
     if args.use_unix_socket and args.use_local_protocol:
         p.error("Cannot use the unix socket and the local protocol at the same time.")
     if args.use_local_protocol:
@@ -73,7 +83,8 @@ def _print_metrics() -> None:
 
 def mnist(n: int, r: int, e: int, show_metrics: bool = True, measure_time: bool = False, model: str = "mlp",
           protocol: str = "memory", partition: str = "iid", alpha: float = 0.5, batch: int = 32,
-          device=None, use_unix_socket: bool = False, aggregator: str = "fedavg") -> List[Node]:
+          device=None, use_unix_socket: bool = False, aggregator: str = "fedavg",
+          dp_clip: Optional[float] = None, dp_noise: float = 0.0) -> List[Node]:
     start = time.time()
     proto = InMemoryCommunicationProtocol if protocol == "memory" else GrpcCommunicationProtocol
     nodes: List[Node] = []
@@ -82,7 +93,9 @@ def mnist(n: int, r: int, e: int, show_metrics: bool = True, measure_time: bool 
         data = MnistFederatedDM(sub_id=i, number_sub=n, batch_size=batch, partitioner=partition, alpha=alpha)
         kw = {"device": device} if device else {}
         addr = f"unix:///tmp/p2pfl_amd-{os.getpid()}-{i}.sock" if use_unix_socket else "127.0.0.1"
-        node = Node(net, data, address=addr, protocol=proto, aggregator=AGGREGATORS[aggregator], **kw)
+        # one mechanism per node, each with its own secret seed
+        privacy = GaussianMechanism(dp_clip, dp_noise) if dp_clip is not None else None
+        node = Node(net, data, address=addr, protocol=proto, aggregator=AGGREGATORS[aggregator], privacy=privacy, **kw)
         node.start()
         nodes.append(node)
     try:
@@ -114,7 +127,8 @@ def main(argv=None) -> None:
     if args.wire_dtype is not None:
         Settings.WIRE_DTYPE = args.wire_dtype
     mnist(args.nodes, args.rounds, args.epochs, args.show_metrics, args.measure_time, args.model, args.protocol,
-          args.partition, args.alpha, args.batch, args.device, args.use_unix_socket, args.aggregator)
+          args.partition, args.alpha, args.batch, args.device, args.use_unix_socket, args.aggregator,
+          args.dp_clip, args.dp_noise)
 
 
 if __name__ == "__main__":

@@ -188,6 +188,76 @@ def q8_raw_table(layout: ParamLayout, device: Any) -> Any:
     return t
 
 
+# Differentially private updates (ops.dp_apply): which elements the mechanism
+# covers, one byte per 64-element block.  Cached like the q8 tables, by
+# (layout, exempt suffixes) for the host bytes and per device for the tensor.
+DP_EXEMPT = ("running_mean", "running_var", "num_batches_tracked")
+_DP_COUNTS: "OrderedDict[Tuple[ParamLayout, Tuple[str, ...]], Tuple[bytes, Tuple[str, ...]]]" = OrderedDict()
+_DP_TABLES: "OrderedDict[Tuple[ParamLayout, Tuple[str, ...], torch.device], torch.Tensor]" = OrderedDict()
+
+
+def dp_exempt_names(layout: ParamLayout, exempt: Iterable[str] = DP_EXEMPT) -> Tuple[str, ...]:
+    """Names of the tensors the mechanism leaves alone: those whose recorded
+    dtype is not floating (BatchNorm's ``num_batches_tracked`` mirrored in the
+    arena) and those whose name ends in one of ``exempt``."""
+    suffixes = tuple(exempt)
+    return tuple(name for name, dt in zip(layout.names, layout.dtypes)
+                 if not _is_float(dt) or (suffixes and name.endswith(suffixes)))
+
+
+def _is_float(dtype: str) -> bool:
+    return dtype.startswith(("float", "bfloat"))
+
+
+def dp_block_counts(layout: ParamLayout, exempt: Iterable[str] = DP_EXEMPT) -> bytes:
+    """One byte per 64-element block of the arena: how many of the block's
+    first elements the mechanism privatises.  64 for a block inside a tensor,
+    ``size % 64`` for a tensor's last block (its padding is copied through), 0
+    for every block of an exempt tensor (:func:`dp_exempt_names`).  Running
+    statistics are exempt by default because a noised variance goes negative;
+    a float tensor that is exempted travels unprotected, which is logged once
+    per layout.  ValueError if the layout is not well formed."""
+    suffixes = tuple(exempt)
+    key = (layout, suffixes)
+    hit = _lru_get(_DP_COUNTS, key)
+    if hit is None:
+        if not layout.well_formed():
+            raise ValueError("malformed parameter layout")
+        skip = set(dp_exempt_names(layout, suffixes))
+        counts = bytearray(layout.numel // ALIGN)
+        for name, off, n in zip(layout.names, layout.offsets, layout.sizes()):
+            if name in skip or n == 0:
+                continue
+            b, full = off // ALIGN, n // ALIGN
+            counts[b : b + full] = bytes([ALIGN]) * full
+            if n % ALIGN:
+                counts[b + full] = n % ALIGN
+        unprotected = tuple(name for name, dt in zip(layout.names, layout.dtypes) if name in skip and _is_float(dt))
+        if unprotected:
+            from p2pfl_amd.management.logger import logger
+
+            logger.warning("privacy", f"{len(unprotected)} float tensors are exempt from the Gaussian mechanism and "
+                           f"travel unprotected: {', '.join(unprotected[:4])}{', ...' if len(unprotected) > 4 else ''}")
+        hit = (bytes(counts), unprotected)
+        _lru_put(_DP_COUNTS, key, hit)
+    return hit[0]
+
+
+def dp_block_table(layout: ParamLayout, exempt: Iterable[str] = DP_EXEMPT, device: Any = "cpu") -> torch.Tensor:
+    """:func:`dp_block_counts` as the ``uint8`` tensor ``ops.dp_delta_sqnorm`` /
+    ``ops.dp_apply`` take on ``device`` (built once per layout and device)."""
+    suffixes = tuple(exempt)
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (layout, suffixes, device)
+    t = _lru_get(_DP_TABLES, key)
+    if t is None:
+        t = torch.frombuffer(bytearray(dp_block_counts(layout, suffixes)), dtype=torch.uint8).to(device)
+        _lru_put(_DP_TABLES, key, t)
+    return t
+
+
 class FlatParams(OrderedDict):
     """Named views into one contiguous fp32 buffer."""
 

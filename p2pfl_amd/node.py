@@ -1,6 +1,7 @@
 """Node facade (reference ``p2pfl/node.py:47-378``).
 
-Public API kept: ``Node(model, data, address, learner, aggregator, protocol)``,
+Public API kept: ``Node(model, data, address, learner, aggregator, protocol)``
+(new: ``privacy=GaussianMechanism(...)``, differentially private updates),
 ``start/stop/connect/disconnect/get_neighbors/assert_running``,
 ``set_data/set_model``, ``set_start_learning(rounds, epochs)``,
 ``set_stop_learning()``; completion is observable as ``node.state.round is
@@ -16,7 +17,7 @@ FedAvg -- as in the reference.
 from __future__ import annotations
 
 import threading
-from typing import Any, Dict, Optional, Type
+from typing import TYPE_CHECKING, Any, Dict, Optional, Type
 
 import torch
 
@@ -37,6 +38,9 @@ from p2pfl_amd.learning.aggregators import Aggregator, FedAvg
 from p2pfl_amd.management.logger import logger
 from p2pfl_amd.node_state import NodeState
 from p2pfl_amd.stages.workflows import LearningWorkflow
+
+if TYPE_CHECKING:
+    from p2pfl_amd.learning.privacy import GaussianMechanism
 
 
 def _default_protocol():
@@ -61,6 +65,7 @@ class Node:
         aggregator: Type[Aggregator] = FedAvg,
         protocol: Optional[Type[CommunicationProtocol]] = None,
         simulation: bool = False,
+        privacy: Optional["GaussianMechanism"] = None,
         **kwargs,
     ) -> None:
         protocol = protocol or _default_protocol()
@@ -77,6 +82,9 @@ class Node:
         self._running = False
         self.state = NodeState(self.addr)
         self.state.simulation = simulation
+        # a learning.privacy.GaussianMechanism: TrainStage then releases a clipped,
+        # noised copy of the trained weights (None: the weights themselves)
+        self.state.privacy = privacy
         self.learning_workflow = LearningWorkflow()
         self._learning_thread: Optional[threading.Thread] = None
         # callables run by the learning thread at every round boundary

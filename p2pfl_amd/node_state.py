@@ -55,6 +55,9 @@ class NodeState:
         self.simulation = False
 
         self.learner: Optional[Any] = None
+        # learning.privacy.GaussianMechanism of this node (None: updates leave as they are);
+        # set once by Node and kept across experiments: its release count keeps adding up
+        self.privacy: Optional[Any] = None
 
         self.models_aggregated: Dict[str, List[str]] = {}
         self.nei_status: Dict[str, int] = {}

@@ -534,3 +534,13 @@ from p2pfl_amd.ops.fused import (  # noqa: E402
 from p2pfl_amd.ops.fused import linear as linear_blas  # noqa: E402,F401  (hipBLASLt comparison path)
 from p2pfl_amd.ops.gemm import gemm, gemm_reference, linear, linear_gelu  # noqa: E402,F401
 from p2pfl_amd.ops.conv import conv2d  # noqa: E402,F401
+from p2pfl_amd.ops.dp import (  # noqa: E402,F401  (csrc/dp_update.hip)
+    DP_BLOCK,
+    DP_NOISE_MAX,
+    dp_apply,
+    dp_apply_reference,
+    dp_delta_sqnorm,
+    dp_delta_sqnorm_reference,
+    dp_noise_reference,
+    philox4x32_reference,
+)

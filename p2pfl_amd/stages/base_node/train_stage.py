@@ -50,7 +50,16 @@ class TrainStage(Stage):
             mark_dead_train_set_members(state, communication_protocol, aggregator)
         if not early_stopping_fn():
             evaluate_and_share(state, communication_protocol)
+        privacy = getattr(state, "privacy", None)
+        start = None
+        if privacy is not None:
+            from p2pfl_amd.learning.step_graph import GATE  # its device work runs under the shared gate
         if not early_stopping_fn():
+            if privacy is not None:
+                # the weights the round starts from: the update that gets clipped is fit()'s
+                # (a device copy: never beside another virtual peer's graph capture)
+                with GATE.shared():
+                    start = state.learner.get_parameters().clone()
             logger.info(state.addr, "Training...")
             with logger.span(state.addr, "fit", round=state.round):
                 state.learner.fit()
@@ -59,6 +68,15 @@ class TrainStage(Stage):
             # the live weights, unordered: the aggregator's kernels read them under the
             # arena's WeightGuard (arena.reading), a one-model round reads nothing
             own = getattr(learner, "live_parameters", learner.get_parameters)()
+            if privacy is not None:
+                # what leaves the node is a clipped, noised copy; the learner keeps its weights
+                rnd = state.round
+                if rnd is None or start is None:  # stopped meanwhile: nothing is released
+                    return StageFactory.get_stage("GossipModelStage")
+                with logger.span(state.addr, "privatize", round=rnd), GATE.shared():
+                    own = privacy.privatize(own, start, rnd)
+                logger.info(state.addr, f"Privacy: {privacy.releases} updates released, epsilon = "
+                            f"{privacy.epsilon():.4g} at delta = {privacy.delta:g}")
             models_added = aggregator.add_model(own, [state.addr], learner.get_num_samples()[0])
             state.changed.bump()
             communication_protocol.broadcast(

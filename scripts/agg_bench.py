@@ -12,6 +12,7 @@ back-to-back calls, every arm warmed up and timed for >= --seconds in total:
 
     python scripts/agg_bench.py [--seconds 0.3] [--rounds 5] [--out table.md]
     python scripts/agg_bench.py --q8 ...    the q8 wire kernels beside the k = 1 weighted sum (q8_main)
+    python scripts/agg_bench.py --dp ...    the differential-privacy kernels beside the k = 2 weighted sum (dp_main)
 
 Prints one JSON line per point and a markdown table (time per call in us,
 min..max over the rounds as the spread, achieved GB/s by the byte counts above).
@@ -124,8 +125,79 @@ def q8_main(args) -> None:
             f.write(table + "\n")
 
 
+def dp_main(args) -> None:
+    """--dp: the differential-privacy kernels beside the k = 2 weighted sum (which
+    moves the same 12n bytes as the clipping apply pass), at the arenas of the
+    MNIST CNN and of ResNet-50 with their own block tables.
+
+        dp_sqnorm       ops.dp_delta_sqnorm(w, w0, table)            8n bytes
+        dp_apply_id     ops.dp_apply, z = 0, update inside the clip  8n + n/64   (w0 is not read)
+        dp_apply_clip   ops.dp_apply, z = 0, update clipped          12n + n/64
+        dp_apply_noise  ops.dp_apply, z = 1, update clipped          12n + n/64
+        wsum_k2         ops.weighted_average([w, w0], [1, 1])        12n bytes
+    """
+    from p2pfl_amd import ops
+    from p2pfl_amd.learning.arena import DP_EXEMPT, dp_block_table, flatten
+    from p2pfl_amd.models import CNN
+    from p2pfl_amd.models.resnet import ResNet50
+
+    rows = []
+    for name, make in (("cnn", CNN), ("resnet50", ResNet50)):
+        layout = flatten(make().state_dict()).layout
+        n, table = layout.numel, dp_block_table(layout, DP_EXEMPT, "cuda")
+        g = torch.Generator(device="cuda").manual_seed(0)
+        w0 = torch.randn(n, device="cuda", generator=g)
+        w = w0 + 0.01 * torch.randn(n, device="cuda", generator=g)
+        out = torch.empty(n, device="cuda")
+        ss = ops.dp_delta_sqnorm(w, w0, table)
+        norm = math.sqrt(float(ss))
+        arms = {
+            "dp_sqnorm": (lambda: ops.dp_delta_sqnorm(w, w0, table), 8 * n),
+            "dp_apply_id": (lambda: ops.dp_apply(w, w0, table, ss, 2 * norm, 0.0, 1, 0, out=out), 8 * n + n // 64),
+            "dp_apply_clip": (lambda: ops.dp_apply(w, w0, table, ss, norm / 2, 0.0, 1, 0, out=out), 12 * n + n // 64),
+            "dp_apply_noise": (lambda: ops.dp_apply(w, w0, table, ss, norm / 2, 1.0, 1, 0, out=out), 12 * n + n // 64),
+            "wsum_k2": (lambda: ops.weighted_average([w, w0], [1.0, 1.0], out=out), 12 * n),
+        }
+        reps = {}
+        for arm, (fn, _) in arms.items():
+            fn()
+            torch.cuda.synchronize()
+            reps[arm] = max(1, math.ceil(args.seconds * 1e6 / args.rounds / batch_us(fn, 2)))
+        samples = {arm: [] for arm in arms}
+        for _ in range(args.rounds):
+            for arm, (fn, _) in arms.items():
+                samples[arm].append(batch_us(fn, reps[arm]))
+        point = {"size": name, "n": n, "covered": int(table.sum())}
+        for arm, (_, moved) in arms.items():
+            s = sorted(samples[arm])
+            med = s[len(s) // 2]
+            point[arm] = {"us": round(med, 1), "min_us": round(s[0], 1), "max_us": round(s[-1], 1),
+                          "GBps": round(moved / med / 1e3, 1), "calls": reps[arm] * args.rounds}
+        print(json.dumps(point), flush=True)
+        rows.append(point)
+        del w, w0, out
+        torch.cuda.empty_cache()
+    arms = ["dp_sqnorm", "dp_apply_id", "dp_apply_clip", "dp_apply_noise", "wsum_k2"]
+    lines = ["| arena | covered elements | " + " | ".join(f"{a} us (min..max) / GB/s" for a in arms)
+             + " | sqnorm / wsum | clip / wsum | noise / wsum | noise / clip |", "|---|---|" + "---|" * (len(arms) + 4)]
+    for p in rows:
+        cells = [f"{p[a]['us']} ({p[a]['min_us']}..{p[a]['max_us']}) / {p[a]['GBps']}" for a in arms]
+        ws = p["wsum_k2"]["us"]
+        lines.append(f"| {p['size']} ({p['n']}) | {p['covered']} | " + " | ".join(cells)
+                     + f" | {p['dp_sqnorm']['us'] / ws:.2f} | {p['dp_apply_clip']['us'] / ws:.2f} | "
+                     f"{p['dp_apply_noise']['us'] / ws:.2f} | {p['dp_apply_noise']['us'] / p['dp_apply_clip']['us']:.2f} |")
+    table_md = "\n".join(lines)
+    print(table_md)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(table_md + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--dp", action="store_true",
+                    help="time ops.dp_delta_sqnorm / ops.dp_apply beside the k = 2 weighted sum instead (CNN and ResNet-50 arenas)")
     ap.add_argument("--q8", action="store_true",
                     help="time ops.q8_encode / ops.q8_decode beside the k = 1 weighted sum instead (CNN and ResNet-50 arenas)")
     ap.add_argument("--seconds", type=float, default=0.3, help="timed work per arm and point, at least")
@@ -140,6 +212,8 @@ def main() -> None:
     ops.ext()
     if args.q8:
         return q8_main(args)
+    if args.dp:
+        return dp_main(args)
     rows = []
     for name in args.sizes.split(","):
         n = SIZES[name]

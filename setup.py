@@ -37,6 +37,11 @@ HIP_FLAGS = [
     "-fno-gpu-rdc",
     "-I" + os.path.join(HERE, "csrc"),
 ]
+# Per-file additions (a later flag wins).  dp_update.hip spells out singly
+# rounded multiplies and adds that a torch fp32 reference reproduces bit for
+# bit; under -ffp-contract=fast hipcc fuses them into fmas whatever the source
+# says, "on" contracts only inside one source expression.
+FILE_FLAGS = {"dp_update.hip": ["-ffp-contract=on"]}
 
 
 def _compile_one(src: str) -> str:
@@ -46,10 +51,11 @@ def _compile_one(src: str) -> str:
     for d in deps:
         with open(d, "rb") as f:
             h.update(f.read())
-    h.update(" ".join(HIP_FLAGS).encode())
+    flags = HIP_FLAGS + FILE_FLAGS.get(os.path.basename(src), [])
+    h.update(" ".join(flags).encode())
     obj = os.path.join(OBJ_DIR, os.path.basename(src) + "." + h.hexdigest()[:12] + ".o")
     if not os.path.exists(obj):
-        cmd = [os.path.join(ROCM, "bin", "hipcc"), *HIP_FLAGS, "-c", src, "-o", obj]
+        cmd = [os.path.join(ROCM, "bin", "hipcc"), *flags, "-c", src, "-o", obj]
         print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     return obj

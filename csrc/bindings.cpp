@@ -272,6 +272,17 @@ uint16_t* opt_bf16(const c10::optional<torch::Tensor>& t, int64_t n) {
   return reinterpret_cast<uint16_t*>(t->data_ptr());
 }
 
+// Bias corrections of step t from the float32 hyperparameters already in h: the kernels
+// accumulate m and v with those (1.f - h.beta2 is not 1 - 0.999), and corrections from the
+// unrounded doubles describe a slightly different optimizer (v_hat = g^2 (1 - 1.3e-5) at
+// t = 1, ~20x the rounding error of the whole update).  The device-side t_dev path of
+// adam_mt_kernel uses the same float32 values.
+void adam_bias_corrections(p2::AdamParams& h, int64_t step) {
+  const double lr = double(h.lr), b1 = double(h.beta1), b2 = double(h.beta2);
+  h.step_size = float(lr / (1.0 - std::pow(b1, double(step))));
+  h.inv_sqrt_bc2 = float(1.0 / std::sqrt(1.0 - std::pow(b2, double(step))));
+}
+
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> pbf,
                double lr, double b1, double b2, double eps, double wd, int64_t step, bool decoupled) {
   for (auto* t : {&p, &g, &m, &v}) check_f32(*t, "adam operand");
@@ -285,8 +296,7 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor 
   h.beta2 = float(b2);
   h.eps = float(eps);
   h.weight_decay = float(wd);
-  h.step_size = float(lr / (1.0 - std::pow(b1, double(step))));
-  h.inv_sqrt_bc2 = float(1.0 / std::sqrt(1.0 - std::pow(b2, double(step))));
+  adam_bias_corrections(h, step);
   h.decoupled = decoupled ? 1 : 0;
   p2::adam_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), opt_bf16(pbf, n),
                 n, h, stream());
@@ -379,8 +389,7 @@ void adam_mt_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, c10::option
   h.beta2 = float(b2);
   h.eps = float(eps);
   h.weight_decay = float(wd);
-  h.step_size = float(lr / (1.0 - std::pow(b1, double(step))));
-  h.inv_sqrt_bc2 = float(1.0 / std::sqrt(1.0 - std::pow(b2, double(step))));
+  adam_bias_corrections(h, step);
   h.decoupled = decoupled ? 1 : 0;
   if (t_dev.has_value() && t_dev->defined()) {
     TORCH_CHECK(t_dev->device() == p.device() && t_dev->scalar_type() == torch::kInt32 && t_dev->numel() == 1,

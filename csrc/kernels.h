@@ -71,6 +71,8 @@ void dp_apply(const float* w, const float* w0, const uint8_t* table, const float
 
 struct AdamParams {
   float lr, beta1, beta2, eps, weight_decay;
+  // both from the float32 lr / beta1 / beta2 above (the values m and v accumulate with),
+  // evaluated in double and rounded once
   float step_size;     // lr / (1 - beta1^t)
   float inv_sqrt_bc2;  // 1 / sqrt(1 - beta2^t)
   int decoupled;

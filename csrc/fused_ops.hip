@@ -486,6 +486,9 @@ void colsum_multi(CsJobs& jobs, hipStream_t s) {
 // row, online max/sum per lane then combined across the wave.
 // Backward: dz = (softmax(z) - onehot(y)) * (*gscale) / N, with the upstream
 // gradient read from device memory (no host sync).
+// A NaN logit or a row of only -inf gives a NaN lse / loss; -inf logits count
+// as probability 0; a label outside [0, K) gives a NaN loss and a NaN dz row
+// (no ignore_index).
 // ---------------------------------------------------------------------------
 template <typename T>
 P2_DEVICE float ld1(const T* p);
@@ -508,23 +511,29 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ z, 
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   const T* zr = z + size_t(row) * K;
+  // m is never NaN (a NaN fails v > m); a NaN logit makes the lane's s NaN and
+  // every rescale below multiplies it (NaN * 0 = NaN), so it reaches wave_sum.
+  // A -inf logit adds nothing: exp(-inf - m) is never evaluated at m = -inf.
   float m = -INFINITY, s = 0.f;
   for (int k = lane; k < K; k += 64) {
     const float v = ld1<T>(zr + k);
     if (v > m) {
-      s = s * __expf(m - v) + 1.f;
+      s = s * (m == -INFINITY ? 0.f : __expf(m - v)) + 1.f;
       m = v;
-    } else {
+    } else if (v != -INFINITY) {
       s += __expf(v - m);
     }
   }
   const float gm = wave_max(m);
-  s = (m == -INFINITY) ? 0.f : s * __expf(m - gm);
-  const float lse = gm + __logf(wave_sum(s));
+  s *= (m == -INFINITY) ? 0.f : __expf(m - gm);
+  const float tot = wave_sum(s);
+  // a row of only -inf has no softmax: NaN, as F.cross_entropy
+  const float lse = (gm == -INFINITY) ? __builtin_nanf("") : gm + __logf(tot);
   if (lane == 0) {
     const int64_t t = y[row];
     lse_out[row] = lse;
-    loss[row] = (t >= 0 && t < K) ? lse - ld1<T>(zr + t) : 0.f;
+    // a label outside [0, K) is an error made visible, as in head.hip: NaN loss (and NaN dz below)
+    loss[row] = (t >= 0 && t < K) ? lse - ld1<T>(zr + t) : __builtin_nanf("");
   }
 }
 
@@ -536,8 +545,9 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ z, 
   const float g = *gscale * inv_n;
   for (int64_t e = blockIdx.x * int64_t(256) + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) {
     const int row = int(e / K), k = int(e % K);
+    const int64_t t = y[row];
     const float p = __expf(ld1<T>(z + e) - lse[row]);
-    st1<T>(dz + e, (p - (y[row] == k ? 1.f : 0.f)) * g);
+    st1<T>(dz + e, (t >= 0 && t < K) ? (p - (t == k ? 1.f : 0.f)) * g : __builtin_nanf(""));
   }
 }
 

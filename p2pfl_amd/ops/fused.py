@@ -330,7 +330,15 @@ class _SoftmaxXent(torch.autograd.Function):
 
 
 def softmax_xent(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """Mean softmax cross-entropy (= ``F.cross_entropy`` with integer labels), fp32 result."""
+    """Mean softmax cross-entropy over all rows, fp32 result: ``F.cross_entropy`` for integer labels in
+    ``[0, K)``, torch's results on non-finite logits included (a NaN or +inf logit, or a row of only
+    -inf, gives a NaN loss; -inf logits count as probability 0).
+
+    ``ignore_index`` is not supported: a label outside ``[0, K)`` (torch's default -100 included) gives
+    a NaN loss for its row, hence a NaN mean, and a NaN gradient row, as the fused classifier head does;
+    the other rows' gradients stay correct.  Drop or relabel such rows before the call.  (Inputs the
+    kernels do not take -- CPU tensors, other dtypes -- go to ``F.cross_entropy`` as it is.)
+    """
     if _native(logits) and logits.dim() == 2 and labels.dtype == torch.int64 and labels.is_cuda:
         return _SoftmaxXent.apply(logits, labels)
     return F.cross_entropy(logits, labels)

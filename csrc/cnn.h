@@ -84,8 +84,25 @@ void conv12_fwd(const uint8_t* x, const int64_t* idx, const float* params, Offse
 
 void gemm_skinny(const uint16_t* A, const uint16_t* Bt, float* slabs, int mrows, int N, int K, int S, hipStream_t s);
 
+// Evaluation passes (forward only, up to kEvalRows images per launch chain):
+// conv2 with one workgroup per (oc half, run of ipw images): the 32 weight rows staged in
+// LDS once, images taken two at a time, P1 double-buffered per pair; bitwise equal to
+// conv2_fwd.  ipw = 0 picks conv2_loop_ipw(B).
+constexpr int kEvalRows = 512;
+// images per workgroup: the fewest that keep the (2, ceil(B / ipw)) grid within the 256
+// CUs -- the kernel's 128 KB of LDS allow one workgroup per CU, so a larger grid would
+// run in two rounds
+inline int conv2_loop_ipw(int B) { return (B + 127) / 128; }
+void conv2_fwd_loop(const uint16_t* p1, const uint16_t* w2r, const float* params, Offsets off, uint16_t* a1,
+                    uint8_t* am2, int B, int ipw, hipStream_t s);
+// FC1 on the tiled MFMA GEMM: slabs[s][m][n] (S x mrows x 2048 fp32, the layout head
+// reduces) = partial sums over K-slice s of A[mrows][3136] . W1bf[2048][3136]^T;
+// mrows a multiple of 128 up to kEvalRows, S = 1..4 (csrc/cnn_fc1_eval.hip)
+void fc1_eval(const uint16_t* A, const uint16_t* W1bf, float* slabs, int mrows, int S, hipStream_t s);
+
 // w2bf non-null: the FC2 weight is read from its bf16 copy [10][2048] (half the
-// bytes of the fp32 master) -- kept current by fc1_conv_adam / pack_shadows
+// bytes of the fp32 master) -- kept current by fc1_conv_adam / pack_shadows.
+// train = 0 (evaluation): B workgroups, no dH, and dlogits receives the logits themselves
 void head(const float* slabs, int S, int mrows, const float* params, Offsets off, const int64_t* labels,
           const int64_t* idx, int B, int train, uint16_t* H, uint16_t* dH, float* dlogits, float* stats,
           const uint16_t* w2bf, hipStream_t s);

@@ -47,6 +47,13 @@ void check_batch(int B, int mrows) {
   TORCH_CHECK(B >= 1 && B <= mrows, "batch ", B, " exceeds mrows ", mrows);
 }
 
+// forward-only (evaluation) launches: whole passes of up to kEvalRows images, rows padded to 128
+void check_eval_batch(int B, int mrows) {
+  TORCH_CHECK(mrows >= 128 && mrows % 128 == 0 && mrows <= p2cnn::kEvalRows, "mrows must be a multiple of 128 up to ",
+              p2cnn::kEvalRows, ", got ", mrows);
+  TORCH_CHECK(B >= 1 && B <= mrows, "batch ", B, " exceeds mrows ", mrows);
+}
+
 const int64_t* idx_ptr(const c10::optional<torch::Tensor>& idx, int B) {
   return optr<int64_t>(idx, torch::kInt64, B, "idx", 8);
 }
@@ -57,8 +64,8 @@ const int64_t* idx_ptr(const c10::optional<torch::Tensor>& idx, int B) {
 void k_conv1_fwd(torch::Tensor x, c10::optional<torch::Tensor> idx, torch::Tensor params, std::vector<int64_t> off,
                  torch::Tensor p1, torch::Tensor am1, c10::optional<torch::Tensor> p1s, int64_t B) {
   const c10::DeviceGuard g(params.device());
-  // training launches (P1s wanted) hold <= 64 images; evaluation launches <= 128
-  TORCH_CHECK(B >= 1 && B <= (p1s.has_value() && p1s->defined() ? 64 : 128), "bad batch");
+  // training launches (P1s wanted) hold <= 64 images; evaluation launches <= kEvalRows
+  TORCH_CHECK(B >= 1 && B <= (p1s.has_value() && p1s->defined() ? 64 : p2cnn::kEvalRows), "bad batch");
   Offsets o = offsets(off);
   TORCH_CHECK(x.numel() % 784 == 0, "x must be [N,1,28,28] uint8");
   if (!idx.has_value()) TORCH_CHECK(x.numel() / 784 >= B, "x has fewer than B rows");
@@ -73,13 +80,40 @@ void k_conv1_fwd(torch::Tensor x, c10::optional<torch::Tensor> idx, torch::Tenso
 void k_conv2_fwd(torch::Tensor p1, torch::Tensor w2r, torch::Tensor params, std::vector<int64_t> off,
                  torch::Tensor a1, torch::Tensor am2, int64_t B, int64_t mrows) {
   const c10::DeviceGuard g(params.device());
-  check_batch(int(B), int(mrows));
+  if (mrows > 128) check_eval_batch(int(B), int(mrows));
+  else check_batch(int(B), int(mrows));
   Offsets o = offsets(off);
   p2cnn::conv2_fwd(reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(p1, torch::kBFloat16, B * 196 * 32, "p1")),
                    reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2r, torch::kBFloat16, 51200, "w2r")),
                    ptr<float>(params, torch::kFloat32, params_end(o), "params"), o,
                    reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(a1, torch::kBFloat16, mrows * 3136, "a1")),
                    ptr<uint8_t>(am2, torch::kUInt8, B * 3136, "am2"), int(B), stream());
+}
+
+// conv2_fwd on the image-loop kernel at any B <= kEvalRows (ipw images per workgroup, 0 = the
+// dispatch rule's choice); mrows = rows of a1
+void k_conv2_fwd_loop(torch::Tensor p1, torch::Tensor w2r, torch::Tensor params, std::vector<int64_t> off,
+                      torch::Tensor a1, torch::Tensor am2, int64_t B, int64_t mrows, int64_t ipw) {
+  const c10::DeviceGuard g(params.device());
+  TORCH_CHECK(mrows >= B && B >= 1 && B <= p2cnn::kEvalRows, "conv2_fwd_loop: bad batch ", B, " for mrows ", mrows);
+  TORCH_CHECK(ipw >= 0 && ipw <= p2cnn::kEvalRows, "conv2_fwd_loop: bad ipw ", ipw);
+  Offsets o = offsets(off);
+  p2cnn::conv2_fwd_loop(reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(p1, torch::kBFloat16, B * 196 * 32, "p1")),
+                        reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2r, torch::kBFloat16, 51200, "w2r")),
+                        ptr<float>(params, torch::kFloat32, params_end(o), "params"), o,
+                        reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(a1, torch::kBFloat16, mrows * 3136, "a1")),
+                        ptr<uint8_t>(am2, torch::kUInt8, B * 3136, "am2"), int(B), int(ipw), stream());
+}
+
+// slabs [S][mrows][2048] fp32 = K-slice partials of A [mrows][3136] . W1bf [2048][3136]^T
+void k_fc1_eval(torch::Tensor A, torch::Tensor W1bf, torch::Tensor slabs, int64_t mrows, int64_t S) {
+  const c10::DeviceGuard g(A.device());
+  TORCH_CHECK(mrows >= 128 && mrows % 128 == 0 && mrows <= p2cnn::kEvalRows,
+              "fc1_eval: mrows must be a multiple of 128 up to ", p2cnn::kEvalRows, ", got ", mrows);
+  TORCH_CHECK(S >= 1 && S <= 4, "fc1_eval: S must be 1..4, got ", S);
+  p2cnn::fc1_eval(reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(A, torch::kBFloat16, mrows * 3136, "A")),
+                  reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(W1bf, torch::kBFloat16, 2048 * 3136, "W1bf")),
+                  ptr<float>(slabs, torch::kFloat32, S * mrows * 2048, "slabs"), int(mrows), int(S), stream());
 }
 
 void k_conv12_fwd(torch::Tensor x, c10::optional<torch::Tensor> idx, torch::Tensor params, std::vector<int64_t> off,
@@ -116,7 +150,8 @@ void k_head(torch::Tensor slabs, int64_t S, int64_t mrows, torch::Tensor params,
             torch::Tensor labels, c10::optional<torch::Tensor> idx, int64_t B, bool train, torch::Tensor H,
             torch::Tensor dH, torch::Tensor dlogits, torch::Tensor stats, c10::optional<torch::Tensor> w2bf) {
   const c10::DeviceGuard g(params.device());
-  check_batch(int(B), int(mrows));
+  if (!train && mrows > 128) check_eval_batch(int(B), int(mrows));
+  else check_batch(int(B), int(mrows));
   Offsets o = offsets(off);
   if (!idx.has_value()) TORCH_CHECK(labels.numel() >= B, "labels has fewer than B rows");
   p2cnn::head(ptr<float>(slabs, torch::kFloat32, S * mrows * 2048, "slabs"), int(S), int(mrows),
@@ -412,6 +447,12 @@ void register_cnn(pybind11::module& m) {
   c.def("init", &p2cnn::init_attributes, "set kernel attributes (call before HIP graph capture)");
   c.def("conv1_fwd", &k_conv1_fwd);
   c.def("conv2_fwd", &k_conv2_fwd);
+  c.def("conv2_fwd_loop", &k_conv2_fwd_loop, pybind11::arg("p1"), pybind11::arg("w2r"), pybind11::arg("params"),
+        pybind11::arg("off"), pybind11::arg("a1"), pybind11::arg("am2"), pybind11::arg("B"), pybind11::arg("mrows"),
+        pybind11::arg("ipw") = 0);
+  c.def("conv2_loop_ipw", [](int64_t B) { return int64_t(p2cnn::conv2_loop_ipw(int(B))); },
+        "images per workgroup conv2_fwd picks for a launch of B > 128 images");
+  c.def("fc1_eval", &k_fc1_eval);
   c.def("conv12_fwd", &k_conv12_fwd);
   c.def("gemm_skinny", &k_gemm_skinny);
   c.def("head", &k_head, pybind11::arg("slabs"), pybind11::arg("S"), pybind11::arg("mrows"), pybind11::arg("params"),

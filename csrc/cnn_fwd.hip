@@ -97,55 +97,144 @@ P2_DEVICE void glds_copy_n(const uint16_t* src, char* dst, int bytes, int wave, 
                                        (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
 }
 
+// NI images (1 or 2) of the LDS-staged conv2 for wave `py` (= pooled row) of a 7-wave block:
+// their P1 at `p1l[i]`, the oc half's 32 weight rows at `wl`, the per-wave pool exchange at
+// `outl`; image i is row b + i of A1 / AM2.  Two images share every weight fragment read
+// (three LDS reads per MFMA pair instead of four) and their two accumulator chains
+// interleave; each chain keeps the one-image k order, so the values do not change.
+template <int NI>
+P2_DEVICE void conv2_lds_images(const char* const (&p1l)[NI], const char* wl, char* outl, const float* __restrict__ b2,
+                                uint16_t* __restrict__ a1, uint8_t* __restrict__ am2, int b, int nh, int py, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  const uint16_t* wrow = reinterpret_cast<const uint16_t*>(wl) + r * kTaps * kC1 + 8 * h;
+  float(*sout)[33] = reinterpret_cast<float(*)[33]>(outl + py * (32 * 33 * 4));
+  const int rr = r < 28 ? r : 27;
+  const int y = 2 * py + (rr >= 14 ? 1 : 0), x = rr >= 14 ? rr - 14 : rr;
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+  f32x16 acc[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc[i] = f32x16{};
+#pragma unroll 10
+  for (int s = 0; s < 50; ++s) {
+    const int t = s >> 1, ky = t / 5, kx = t % 5, ic = (s & 1) * 16;
+    const int iy = y + ky - 2, ix = x + kx - 2;
+    const bool ok = iy >= 0 && iy < 14 && ix >= 0 && ix < 14;
+    const int po = (ok ? iy * 14 + ix : 0) * kC1 + ic + 8 * h;
+    uint4 v[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) v[i] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p1l[i]) + po);
+    const uint4 bq = *reinterpret_cast<const uint4*>(wrow + t * kC1 + ic);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) acc[i] = mfma32(ok ? v[i] : z4, bq, acc[i]);
+  }
+#pragma unroll
+  for (int im = 0; im < NI; ++im) {
+    // (the exchange is per wave and a wave's LDS accesses stay in order: image 1's stores
+    // follow image 0's reads without a barrier of their own)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = acc_row(i, h);
+      if (row < 28) sout[row][r] = acc[im][i];
+    }
+    __syncthreads();
+    for (int e = lane; e < 7 * 32; e += 64) {
+      const int oc = e / 7, px = e % 7;
+      const float v[4] = {sout[2 * px][oc], sout[2 * px + 1][oc], sout[14 + 2 * px][oc], sout[15 + 2 * px][oc]};
+      float best = v[0];
+      int arg = 0;
+#pragma unroll
+      for (int d = 1; d < 4; ++d)
+        if (v[d] > best) {
+          best = v[d];
+          arg = d;
+        }
+      best += b2[nh * 32 + oc];
+      const size_t o = size_t(b + im) * kFeat + (nh * 32 + oc) * 49 + py * 7 + px;
+      a1[o] = f32_to_bf16(fmaxf(best, 0.f));
+      am2[o] = best > 0.f ? uint8_t(arg) : uint8_t(4);
+    }
+  }
+}
+
 __global__ __launch_bounds__(448) void conv2_fwd_lds_kernel(const uint16_t* __restrict__ p1,
                                                             const uint16_t* __restrict__ w2r,
                                                             const float* __restrict__ b2, uint16_t* __restrict__ a1,
                                                             uint8_t* __restrict__ am2) {
   __shared__ __attribute__((aligned(16))) char smem[kC2Lds];
   const int nh = blockIdx.x, b = blockIdx.y;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-  const int py = wave;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   glds_copy_n(p1 + size_t(b) * 196 * kC1, smem, kC2P1, wave, 7, lane);
   glds_copy_n(w2r + size_t(nh * 32) * kTaps * kC1, smem + kC2P1, kC2W, wave, 7, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const uint16_t* img = reinterpret_cast<const uint16_t*>(smem) + 8 * h;
-  const uint16_t* wrow = reinterpret_cast<const uint16_t*>(smem + kC2P1) + r * kTaps * kC1 + 8 * h;
-  float(*sout)[33] = reinterpret_cast<float(*)[33]>(smem + kC2P1 + kC2W + wave * (32 * 33 * 4));
-  const int rr = r < 28 ? r : 27;
-  const int y = 2 * py + (rr >= 14 ? 1 : 0), x = rr >= 14 ? rr - 14 : rr;
-  const uint4 z4 = make_uint4(0, 0, 0, 0);
-  f32x16 acc = {};
-#pragma unroll 10
-  for (int s = 0; s < 50; ++s) {
-    const int t = s >> 1, ky = t / 5, kx = t % 5, ic = (s & 1) * 16;
-    const int iy = y + ky - 2, ix = x + kx - 2;
-    const bool ok = iy >= 0 && iy < 14 && ix >= 0 && ix < 14;
-    const uint4 v = *reinterpret_cast<const uint4*>(img + (ok ? iy * 14 + ix : 0) * kC1 + ic);
-    const uint4 bq = *reinterpret_cast<const uint4*>(wrow + t * kC1 + ic);
-    acc = mfma32(ok ? v : z4, bq, acc);
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = acc_row(i, h);
-    if (row < 28) sout[row][r] = acc[i];
-  }
+  const char* const img[1] = {smem};
+  conv2_lds_images<1>(img, smem + kC2P1, smem + kC2P1 + kC2W, b2, a1, am2, b, nh, wave, lane);
+}
+
+// The same for a run of images per workgroup (the evaluation passes' 300- and 500-image
+// launches): grid (2, ceil(B / ipw)); workgroup (nh, g) stages its 32 weight rows once
+// and walks images g * ipw .. min(B, (g + 1) * ipw) - 1 two at a time, so the 50 KB of
+// weights are fetched once per run instead of once per image, and read from LDS once per
+// image pair.  P1 is double-buffered by pair: the next pair's 2 x 12.25 KB are in flight
+// (global_load_lds) while this one computes.  Each image runs conv2_fwd_lds_kernel's MFMA
+// sequence and epilogue: A1 / AM2 stay bitwise equal to the two kernels above.
+constexpr int kC2LoopLds = 4 * kC2P1 + kC2W + kC2Out;  // 130944 B: one workgroup per CU
+
+// glds_copy_n with the DMA issued from inline asm: the compiler cannot tell which LDS
+// bytes a builtin DMA writes and would wait for it (vmcnt(0)) at the next LDS read, the
+// current image's first fragment.  The caller waits (vmcnt(0) + barrier) before the first
+// read of `dst`.
+P2_DEVICE void glds_prefetch_n(const uint16_t* src, char* dst, int bytes, int wave, int nwaves, int lane) {
+  for (int c = wave; c * 1024 < bytes; c += nwaves)
+    if (c * 1024 + lane * 16 < bytes) {
+      const uint32_t m0v = __builtin_amdgcn_readfirstlane(uint32_t(reinterpret_cast<uintptr_t>(dst + c * 1024)));
+      const void* g = src + c * 512 + lane * 8;
+      uint32_t keep;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\t"
+          "s_mov_b32 m0, %2\n\t"
+          "s_nop 0\n\t"
+          "global_load_lds_dwordx4 %1, off\n\t"
+          "s_mov_b32 m0, %0"
+          : "=&s"(keep)
+          : "v"(g), "s"(m0v)
+          : "memory");
+    }
+}
+
+__global__ __launch_bounds__(448) void conv2_fwd_loop_kernel(const uint16_t* __restrict__ p1,
+                                                             const uint16_t* __restrict__ w2r,
+                                                             const float* __restrict__ b2, uint16_t* __restrict__ a1,
+                                                             uint8_t* __restrict__ am2, int B, int ipw) {
+  __shared__ __attribute__((aligned(16))) char smem[kC2LoopLds];  // [2 pairs x 2 P1 | W | pool exchange]
+  const int nh = blockIdx.x, b0 = blockIdx.y * ipw, n = min(ipw, B - b0);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  char* const wl = smem + 4 * kC2P1;
+  // images [i, min(n, i + 2)) of the run into pair buffer `pb`
+  auto stage_pair = [&](int i, int pb, bool first) {
+    for (int j = 0; j < 2 && i + j < n; ++j) {
+      const uint16_t* src = p1 + size_t(b0 + i + j) * 196 * kC1;
+      char* dst = smem + (2 * pb + j) * kC2P1;
+      if (first) glds_copy_n(src, dst, kC2P1, wave, 7, lane);
+      else glds_prefetch_n(src, dst, kC2P1, wave, 7, lane);
+    }
+  };
+  stage_pair(0, 0, true);
+  glds_copy_n(w2r + size_t(nh * 32) * kTaps * kC1, wl, kC2W, wave, 7, lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  for (int e = lane; e < 7 * 32; e += 64) {
-    const int oc = e / 7, px = e % 7;
-    const float v[4] = {sout[2 * px][oc], sout[2 * px + 1][oc], sout[14 + 2 * px][oc], sout[15 + 2 * px][oc]};
-    float best = v[0];
-    int arg = 0;
-#pragma unroll
-    for (int d = 1; d < 4; ++d)
-      if (v[d] > best) {
-        best = v[d];
-        arg = d;
-      }
-    best += b2[nh * 32 + oc];
-    const size_t o = size_t(b) * kFeat + (nh * 32 + oc) * 49 + py * 7 + px;
-    a1[o] = f32_to_bf16(fmaxf(best, 0.f));
-    am2[o] = best > 0.f ? uint8_t(arg) : uint8_t(4);
+  for (int i = 0, pb = 0; i < n; i += 2, pb ^= 1) {
+    // the other pair buffer was last read by the pair before, which every wave left at the barrier below
+    if (i + 2 < n) stage_pair(i + 2, pb ^ 1, false);
+    const char* const img[2] = {smem + (2 * pb) * kC2P1, smem + (2 * pb + 1) * kC2P1};
+    if (i + 1 < n) {
+      conv2_lds_images<2>(img, wl, wl + kC2W, b2, a1, am2, b0 + i, nh, wave, lane);
+    } else {
+      const char* const one[1] = {img[0]};
+      conv2_lds_images<1>(one, wl, wl + kC2W, b2, a1, am2, b0 + i, nh, wave, lane);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   }
 }
 
@@ -338,6 +427,13 @@ void conv12_fwd(const uint8_t* x, const int64_t* idx, const float* params, Offse
 
 void init_fwd_attributes() {}
 
+void conv2_fwd_loop(const uint16_t* p1, const uint16_t* w2r, const float* params, Offsets off, uint16_t* a1,
+                    uint8_t* am2, int B, int ipw, hipStream_t s) {
+  if (ipw < 1) ipw = conv2_loop_ipw(B);
+  hipLaunchKernelGGL(conv2_fwd_loop_kernel, dim3(2, (B + ipw - 1) / ipw), dim3(448), 0, s, p1, w2r,
+                     params + off.c2b, a1, am2, B, ipw);
+}
+
 void conv2_fwd(const uint16_t* p1, const uint16_t* w2r, const float* params, Offsets off, uint16_t* a1,
                uint8_t* am2, int B, hipStream_t s) {
   // P2CNN_CONV2_FWD_LDS=1: the LDS-staged kernel -- measured slower, 8.2 vs 6.0 us
@@ -349,7 +445,10 @@ void conv2_fwd(const uint16_t* p1, const uint16_t* w2r, const float* params, Off
   }();
   // ... but at the evaluation passes' 128-image launches the staged copy is reused by
   // 7 waves x 2 blocks per image and wins: 9.2 vs 14.1 us (scripts/eval_fwd_probe.py)
-  if (lds || B > 64)
+  // past 128 images (one evaluation pass per launch) a workgroup walks a run of images
+  if (B > 128)
+    conv2_fwd_loop(p1, w2r, params, off, a1, am2, B, 0, s);
+  else if (lds || B > 64)
     hipLaunchKernelGGL(conv2_fwd_lds_kernel, dim3(2, B), dim3(448), 0, s, p1, w2r, params + off.c2b, a1, am2);
   else
     hipLaunchKernelGGL(conv2_fwd_kernel, dim3(7, 2, B), dim3(64), 0, s, p1, w2r, params + off.c2b, a1, am2);
@@ -575,7 +674,8 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ sla
     for (int c = 0; c < kCls; ++c) {
       const float g = (__expf(lg[c] - lse) - (c == y ? 1.f : 0.f)) * invB;
       dl[c] = g;
-      if (train) dlogits[b * kCls + c] = g;
+      // an evaluation launch leaves the sample's logits there instead (per-sample predictions)
+      dlogits[b * kCls + c] = train ? g : lg[c];
     }
   }
   if (!train) return;

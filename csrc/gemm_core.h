@@ -439,7 +439,8 @@ P2_DEVICE void bn_epilogue_reduce(const GemmParams& p, Moments mo, int tm, int t
 // kernels that produce a BN input instantiate it, the Linear GEMMs do not)
 // EPI (epilogue_kind): 0 compact epilogue for plain stores, 2 bias only (see
 // gemm_pp.hip's note on instruction fetch); 1 every epilogue feature behind
-// runtime flags.
+// runtime flags; 3 raw split-K partials as row-major fp32 slabs at c + slice * M * ldc,
+// nothing else (csrc/cnn_fc1_eval.hip).
 // A loader sees the output tile it serves through tile_bound (default: itself);
 // a loader whose gather depends on the tile's rows -- the stride-2 input
 // gradient's B operand takes the taps of its tile's output phase (conv.hip) --
@@ -617,6 +618,24 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
   const int h = lane >> 5;
   auto row_of = [&](int i) { return m0 + wm * 32 * FM + i * 32 + (lane & 31); };
   auto col_of = [&](int j, int g) { return n0 + wn * 32 * FN + j * 32 + 8 * g + 4 * h; };
+  if constexpr (EPI == 3) {
+    // every K-slice writes its raw fp32 partial row-major to c + slice * M * ldc: the
+    // slab form a later kernel reduces by plain row reads (the MNIST-CNN head), at
+    // 16-B stores scattered over 32 rows per instruction instead of SlabGeom's 1 KB
+    float* slab = reinterpret_cast<float*>(p.c) + int64_t(split) * p.M * p.ldc;
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int m = row_of(i), n = col_of(j, g);
+          if (m < p.M && n < p.N)
+            *reinterpret_cast<f32x4*>(slab + int64_t(m) * p.ldc + n) =
+                f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+        }
+    return;
+  }
   if (EPI == 1 && p.splits > 1) {
     // every K-slice writes its raw fp32 partial tile, fragment-native (SlabGeom)
     using SG = SlabGeom<CFG>;

@@ -58,6 +58,12 @@ _EVAL_LOW = os.environ.get("P2PFL_EVAL_STREAM_LOW", "1") != "0"
 # stream of its own).  In line: no stream hand-offs between the epoch and its
 # validation pass (1-peer round: in line 6.65 vs 7.23 ms, profiles/r5_handoff_probe.md).
 _EVAL_SIDE = os.environ.get("P2PFL_EVAL_SIDE_STREAM", "0")
+# samples per evaluation launch chain (a multiple of 128 up to 512; read when a learner is
+# built).  Above 128 a chunk runs conv2 on the image-loop kernel and FC1 on the tiled MFMA
+# GEMM (csrc/cnn_fc1_eval.hip), so the 500-sample test pass and the 300-sample validation
+# pass are 4 launches each instead of 16 and 12; "128": 128-sample chunks through
+# gemm_skinny, the path before (profiles/cnn_eval_pass.md).
+EVAL_ROWS = int(os.environ.get("P2PFL_EVAL_ROWS", "512"))
 # conv1 + conv2 in one launch (csrc/cnn_fwd.hip conv12_fwd_kernel: each pooled-row block
 # recomputes the P1 rows its conv2 reads in LDS; no P1 round trip, one launch less).
 # Opt-in (P2PFL_CNN_CONV12=1): measured slower, 16.3 us vs 4.6 + 6.0 us for the two
@@ -416,25 +422,38 @@ class _EvalSnapshot:
 
 
 class _EvalForward:
-    """Forward-only view of a :class:`FusedCNNEngine` at 128 samples per launch.
+    """Forward-only view of a :class:`FusedCNNEngine` at up to ``EVAL_ROWS`` samples per launch chain.
 
-    Evaluation has no optimizer step between batches, so it runs the same
-    forward kernels (reading a :class:`_EvalSnapshot` of the engine's fp32
-    parameters and bf16 shadows) on 128-sample batches: a quarter of the
-    launches per pass, and the FC1 GEMM -- bound by streaming its 12.8 MB
-    weight -- costs little more per launch at 128 rows than at 32.
-    Per-sample losses and predictions do not depend on how the set is batched.
+    Evaluation has no optimizer step between batches, so a pass is cut into
+    chunks of at most ``EVAL_ROWS`` samples (512: the 500-sample test pass and
+    the 300-sample validation pass are one chain each) and every chunk runs
+    conv1 -> conv2 (image-loop kernel) -> ``fc1_eval`` (tiled MFMA GEMM, the
+    12.8 MB W1 shadow streamed once per chunk) -> head, reading a
+    :class:`_EvalSnapshot` of the engine's fp32 parameters and bf16 shadows.
+    FC1 runs on the chunk's rows rounded up to 128; the padding rows of A1 hold
+    whatever an earlier chunk left there (zeros at first), which only reaches
+    the same rows of the slabs -- a GEMM row depends on its own A row alone --
+    and the head launches one workgroup per real sample.  ``EVAL_ROWS = 128``
+    is the earlier path: 128-sample chunks through ``gemm_skinny`` at the
+    engine's 7 K-slices.  Per-sample losses and predictions do not depend on
+    how the set is batched (up to the fp32 summation order of FC1).
     """
 
-    MROWS = 128
+    FC1_SPLITS = 4  # K-slices of fc1_eval: 4 x 16 tiles x 4 = one workgroup per CU at 512 rows
 
     def __init__(self, eng: FusedCNNEngine) -> None:
         self.eng = eng
-        M, dev, bf = self.MROWS, eng.device, torch.bfloat16
+        rows = int(EVAL_ROWS)
+        if rows < 128 or rows % 128 or rows > 512:
+            raise ValueError(f"P2PFL_EVAL_ROWS must be 128, 256, 384 or 512, got {rows}")
+        self.rows = rows
+        self.tiled = rows > 128
+        self.S = self.FC1_SPLITS if self.tiled else eng.S1
+        M, dev, bf = rows, eng.device, torch.bfloat16
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
         self.p1, self.am1 = z(M * 196 * 32, dt=bf), z(M * 196 * 32, dt=torch.uint8)
         self.a1, self.am2 = z(M * FEAT, dt=bf), z(M * FEAT, dt=torch.uint8)
-        self.slabs1 = z(eng.S1 * M * HID)
+        self.slabs1 = z(self.S * M * HID)
         self.H, self.dH = z(M * HID, dt=bf), z(M * HID, dt=bf)
         self.dlogits = z(M * 10)
         self.snaps: Dict[str, _EvalSnapshot] = {}
@@ -447,14 +466,18 @@ class _EvalForward:
 
     def forward(self, x: torch.Tensor, labels: torch.Tensor, idx: Optional[torch.Tensor], B: int, stats: torch.Tensor,
                 snap: _EvalSnapshot) -> None:
-        e, C, M = self.eng, self.eng.C, self.MROWS
-        if _CONV12:
+        e, C = self.eng, self.eng.C
+        M = -(-B // 128) * 128 if self.tiled else 128  # FC1 rows of this chunk
+        if _CONV12 and not self.tiled:
             C.conv12_fwd(x, idx, snap.params, e.off, snap.w2r, None, self.am1, None, self.a1, self.am2, B, M)
         else:
             C.conv1_fwd(x, idx, snap.params, e.off, self.p1, self.am1, None, B)
             C.conv2_fwd(self.p1, snap.w2r, snap.params, e.off, self.a1, self.am2, B, M)
-        C.gemm_skinny(self.a1, snap.w1bf, self.slabs1, M, HID, FEAT, e.S1)
-        C.head(self.slabs1, e.S1, M, snap.params, e.off, labels, idx, B, False, self.H, self.dH, self.dlogits, stats,
+        if self.tiled:
+            C.fc1_eval(self.a1, snap.w1bf, self.slabs1, M, self.S)
+        else:
+            C.gemm_skinny(self.a1, snap.w1bf, self.slabs1, M, HID, FEAT, self.S)
+        C.head(self.slabs1, self.S, M, snap.params, e.off, labels, idx, B, False, self.H, self.dH, self.dlogits, stats,
                snap.w2bf)
 
 
@@ -529,7 +552,7 @@ class FusedCNNLearner(TorchLearner):
 
     def _graph_key(self, name: str, loader, train: bool):
         n = len(loader.dataset)
-        B = loader.batch_size if train else _EvalForward.MROWS
+        B = loader.batch_size if train else self._eval_fwd.rows
         return self._plan(n, B), (name, n, B, loader.x.data_ptr(), loader.y.data_ptr())
 
     def _ensure_graph(self, name: str, loader, train: bool) -> "_EpochGraph":

@@ -191,4 +191,9 @@ void register_bn(pybind11::module& m) {
         py::arg("relu"), py::arg("need_dres"), py::arg("counters") = py::none(), py::arg("dy2") = py::none());
   f.def("fused_rows", [](int64_t M, int64_t C) { return p2bn::bn_fused_plan(int(M), int(C)).S; },
         "partial rows of the statistics + finalize kernels for an [M, C] activation (0: not eligible)");
+  f.def("plan", [](int64_t M, int64_t C) {
+          const auto p = p2bn::bn_plan(int(M), int(C));
+          return std::make_tuple(p.tpr, p.rp, p.gx, p.S);
+        },
+        "(tpr, rp, gx, S): launch geometry of the separate statistics kernels for an [M, C] activation");
 }

@@ -419,7 +419,8 @@ P2_DEVICE void bn_epilogue_reduce(const GemmParams& p, Moments mo, int tm, int t
     return;
   }
   // finalize column n (same outputs as bn_finalize_fwd_kernel)
-  const float var = fmaxf(acc.m2 / M, 0.f);
+  const float v0 = acc.m2 / M;
+  const float var = v0 < 0.f ? 0.f : v0;  // not fmaxf: a NaN stays a NaN
   const float rs = rsqrtf(var + e.eps);
   e.mean[n] = acc.mean;
   e.rstd[n] = rs;
@@ -860,7 +861,8 @@ P2_DEVICE void gemm_body(const GemmParams& p, const LA& la0, const LB& lb0, int 
           mo = bn_merge(true, mo, Moments{cnt, src[1], src[2]});
         } else if (cnt > 0.f) {
           const float mu = src[1] / cnt;
-          mo = moments_merge(mo, Moments{cnt, src[0] + mu, fmaxf(src[2] - src[1] * mu, 0.f)});
+          const float m2 = src[2] - src[1] * mu;
+          mo = moments_merge(mo, Moments{cnt, src[0] + mu, m2 < 0.f ? 0.f : m2});  // NaN stays NaN
         }
       }
     }

@@ -283,13 +283,7 @@ void adam_bias_corrections(p2::AdamParams& h, int64_t step) {
   h.inv_sqrt_bc2 = float(1.0 / std::sqrt(1.0 - std::pow(b2, double(step))));
 }
 
-void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> pbf,
-               double lr, double b1, double b2, double eps, double wd, int64_t step, bool decoupled) {
-  for (auto* t : {&p, &g, &m, &v}) check_f32(*t, "adam operand");
-  const int64_t n = p.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam: size mismatch");
-  TORCH_CHECK(n % 4 == 0, "adam: arena length must be a multiple of 4");
-  const c10::DeviceGuard guard(p.device());
+p2::AdamParams adam_params(double lr, double b1, double b2, double eps, double wd, int64_t step, bool decoupled) {
   p2::AdamParams h{};
   h.lr = float(lr);
   h.beta1 = float(b1);
@@ -298,6 +292,25 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor 
   h.weight_decay = float(wd);
   adam_bias_corrections(h, step);
   h.decoupled = decoupled ? 1 : 0;
+  return h;
+}
+
+// SGD's optional momentum buffer: null when absent, else an fp32 arena of n elements
+float* opt_buf(c10::optional<torch::Tensor>& buf, int64_t n) {
+  if (!buf.has_value() || !buf->defined()) return nullptr;
+  check_f32(*buf, "buf");
+  TORCH_CHECK(buf->numel() == n, "sgd: buf size mismatch");
+  return buf->data_ptr<float>();
+}
+
+void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> pbf,
+               double lr, double b1, double b2, double eps, double wd, int64_t step, bool decoupled) {
+  for (auto* t : {&p, &g, &m, &v}) check_f32(*t, "adam operand");
+  const int64_t n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam: size mismatch");
+  TORCH_CHECK(n % 4 == 0, "adam: arena length must be a multiple of 4");
+  const c10::DeviceGuard guard(p.device());
+  const p2::AdamParams h = adam_params(lr, b1, b2, eps, wd, step, decoupled);
   p2::adam_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), opt_bf16(pbf, n),
                 n, h, stream());
 }
@@ -308,12 +321,7 @@ void sgd_step(torch::Tensor p, torch::Tensor g, c10::optional<torch::Tensor> buf
   check_f32(g, "g");
   const int64_t n = p.numel();
   TORCH_CHECK(g.numel() == n && n % 4 == 0, "sgd: size mismatch");
-  float* b = nullptr;
-  if (buf.has_value() && buf->defined()) {
-    check_f32(*buf, "buf");
-    TORCH_CHECK(buf->numel() == n, "sgd: buf size mismatch");
-    b = buf->data_ptr<float>();
-  }
+  float* b = opt_buf(buf, n);
   const c10::DeviceGuard guard(p.device());
   p2::SgdParams h{float(lr), float(momentum), float(dampening), float(wd), nesterov ? 1 : 0, first_step ? 1 : 0};
   p2::sgd_step(p.data_ptr<float>(), g.data_ptr<float>(), b, opt_bf16(pbf, n), n, h, stream());
@@ -383,14 +391,7 @@ void adam_mt_step(torch::Tensor p, torch::Tensor m, torch::Tensor v, c10::option
   check_tables(tens, chunks, p.device());
   const c10::DeviceGuard guard(p.device());
   auto gp = grad_ptrs(gtab, grads, numels, grad_bf16, grad_cl, tens, p.device());
-  p2::AdamParams h{};
-  h.lr = float(lr);
-  h.beta1 = float(b1);
-  h.beta2 = float(b2);
-  h.eps = float(eps);
-  h.weight_decay = float(wd);
-  adam_bias_corrections(h, step);
-  h.decoupled = decoupled ? 1 : 0;
+  p2::AdamParams h = adam_params(lr, b1, b2, eps, wd, step, decoupled);
   if (t_dev.has_value() && t_dev->defined()) {
     TORCH_CHECK(t_dev->device() == p.device() && t_dev->scalar_type() == torch::kInt32 && t_dev->numel() == 1,
                 "t_dev must be an int32 [1] tensor on the arena's device");
@@ -409,12 +410,7 @@ void sgd_mt_step(torch::Tensor p, c10::optional<torch::Tensor> buf, c10::optiona
                  double dampening, double wd, bool nesterov, bool first_step, c10::optional<torch::Tensor> gtab) {
   check_f32(p, "p");
   const int64_t n = p.numel();
-  float* b = nullptr;
-  if (buf.has_value() && buf->defined()) {
-    check_f32(*buf, "buf");
-    TORCH_CHECK(buf->numel() == n, "sgd: buf size mismatch");
-    b = buf->data_ptr<float>();
-  }
+  float* b = opt_buf(buf, n);
   check_tables(tens, chunks, p.device());
   const c10::DeviceGuard guard(p.device());
   auto gp = grad_ptrs(gtab, grads, numels, grad_bf16, grad_cl, tens, p.device());

@@ -1,85 +1,154 @@
-// Whole-arena fused optimizer steps (Adam / AdamW / SGD-momentum).
+// Fused optimizer steps (Adam / AdamW / SGD-momentum) over flat arenas.
 //
 // torch.optim (and the reference's Lightning loop, cnn.py:89-91) update each
 // parameter tensor with its own kernel(s).  With parameters, gradients and
 // optimizer state laid out as flat arenas the full update is one streaming
 // pass: float4 loads of p, g, m, v; fp32 math; float4 stores; optional bf16
 // shadow copy of p for bf16 MFMA consumers (saves a separate cast kernel).
+//
+// Each piece exists once: an update rule per optimizer (AdamRule, SgdRule), the
+// element helpers that move a rule's state between memory and registers, one
+// whole-arena traversal and one multi-tensor traversal.  The __global__ kernels
+// are wrappers that pick a rule and a traversal.
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
 
 namespace p2 {
 
+// ---- update rules ----------------------------------------------------------
+// A rule holds its hyperparameters and the bases of its kStates fp32 state
+// arenas (indexed like p), says whether a state array is there at all, and
+// updates one element held in registers: p and its state s[kStates], given g.
+struct AdamRule {
+  static constexpr int kStates = 2;  // m, v
+  AdamParams h;
+  float* s[kStates];
+  P2_DEVICE bool has(int) const { return true; }
+  P2_DEVICE void apply(float& p, float g, float (&ms)[kStates]) const {
+    float &m = ms[0], &v = ms[1];
+    if (h.weight_decay != 0.f) {
+      if (h.decoupled)
+        p *= (1.f - h.lr * h.weight_decay);
+      else
+        g = fmaf(h.weight_decay, p, g);
+    }
+    m = fmaf(h.beta1, m, (1.f - h.beta1) * g);
+    v = fmaf(h.beta2, v, (1.f - h.beta2) * g * g);
+    p = p - h.step_size * (m / (sqrtf(v) * h.inv_sqrt_bc2 + h.eps));
+  }
+};
+
+struct SgdRule {
+  static constexpr int kStates = 1;  // momentum buffer; null without momentum
+  SgdParams h;
+  float* s[kStates];
+  P2_DEVICE bool has(int) const { return s[0] != nullptr; }
+  P2_DEVICE void apply(float& p, float g, float (&bs)[kStates]) const {
+    float& b = bs[0];
+    if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
+    if (has(0)) {
+      b = h.first_step ? g : fmaf(h.momentum, b, (1.f - h.dampening) * g);
+      g = h.nesterov ? fmaf(h.momentum, b, g) : b;
+    }
+    p = fmaf(-h.lr, g, p);
+  }
+};
+
+// ---- element helpers ---------------------------------------------------------
+// Everything stays in registers: the arrays are indexed by unrolled constants
+// only (a pointer to a local would put the state on the stack).
+P2_DEVICE void load_grad4(const void* g, bool bf, int64_t i, float (&o)[4]) {
+  if (bf) {
+    const uint2 u = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(g) + i);
+    o[0] = __uint_as_float(u.x << 16);
+    o[1] = __uint_as_float(u.x & 0xffff0000u);
+    o[2] = __uint_as_float(u.y << 16);
+    o[3] = __uint_as_float(u.y & 0xffff0000u);
+  } else {
+    const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(g) + i);
+    o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
+  }
+}
+P2_DEVICE float load_grad1(const void* g, bool bf, int64_t i) {
+  return bf ? bf16_to_f32(static_cast<const uint16_t*>(g)[i]) : static_cast<const float*>(g)[i];
+}
+P2_DEVICE void store_bf16x4(uint16_t* q, const float (&v)[4]) {
+  uint2 o;
+  o.x = pack_bf16x2(v[0], v[1]);
+  o.y = pack_bf16x2(v[2], v[3]);
+  *reinterpret_cast<uint2*>(q) = o;
+}
+
+// Element i of the arenas: p and the rule's state into registers / back.
+template <class Rule>
+P2_DEVICE void load1(const Rule& r, const float* p, int64_t i, float& pv, float (&sv)[Rule::kStates]) {
+  pv = p[i];
+#pragma unroll
+  for (int k = 0; k < Rule::kStates; ++k) sv[k] = r.has(k) ? r.s[k][i] : 0.f;
+}
+template <class Rule>
+P2_DEVICE void store1(const Rule& r, float* p, int64_t i, float pv, const float (&sv)[Rule::kStates]) {
+  p[i] = pv;
+#pragma unroll
+  for (int k = 0; k < Rule::kStates; ++k)
+    if (r.has(k)) r.s[k][i] = sv[k];
+}
+// One step of element i; returns the new p.
+template <class Rule>
+P2_DEVICE float step1(const Rule& r, float* p, int64_t i, float g) {
+  float pv, sv[Rule::kStates];
+  load1(r, p, i, pv, sv);
+  r.apply(pv, g, sv);
+  store1(r, p, i, pv, sv);
+  return pv;
+}
+// Elements i .. i + 3 (16-byte aligned) as float4 accesses.
+template <class Rule>
+P2_DEVICE void load4(const Rule& r, const float* p, int64_t i, float (&pv)[4], float (&sv)[4][Rule::kStates]) {
+  const float4 pp = *reinterpret_cast<const float4*>(p + i);
+  pv[0] = pp.x; pv[1] = pp.y; pv[2] = pp.z; pv[3] = pp.w;
+#pragma unroll
+  for (int k = 0; k < Rule::kStates; ++k) {
+    const float4 t = r.has(k) ? *reinterpret_cast<const float4*>(r.s[k] + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    sv[0][k] = t.x; sv[1][k] = t.y; sv[2][k] = t.z; sv[3][k] = t.w;
+  }
+}
+// The step on the 4 elements load4 left in registers, and their new p and state back to memory.
+template <class Rule>
+P2_DEVICE void step4(const Rule& r, float* p, int64_t i, const float (&g)[4], float (&pv)[4],
+                     float (&sv)[4][Rule::kStates]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r.apply(pv[e], g[e], sv[e]);
+  *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+#pragma unroll
+  for (int k = 0; k < Rule::kStates; ++k)
+    if (r.has(k)) *reinterpret_cast<float4*>(r.s[k] + i) = make_float4(sv[0][k], sv[1][k], sv[2][k], sv[3][k]);
+}
+
+// ---- whole-arena traversal ------------------------------------------------------
+template <class Rule>
+P2_DEVICE void arena_body(const Rule& r, float* p, const float* g, uint16_t* pbf, int64_t n4) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float gg[4], pv[4], sv[4][Rule::kStates];
+    load_grad4(g, false, 4 * i, gg);
+    load4(r, p, 4 * i, pv, sv);
+    step4(r, p, 4 * i, gg, pv, sv);
+    if (pbf) store_bf16x4(pbf + 4 * i, pv);
+  }
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    uint16_t* __restrict__ pbf, int64_t n4, AdamParams h) {
-  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-    float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 mm = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    float* P = &pp.x;
-    float* G = &gg.x;
-    float* M = &mm.x;
-    float* V = &vv.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gj = G[j];
-      if (h.weight_decay != 0.f) {
-        if (h.decoupled)
-          P[j] *= (1.f - h.lr * h.weight_decay);
-        else
-          gj = fmaf(h.weight_decay, P[j], gj);
-      }
-      M[j] = fmaf(h.beta1, M[j], (1.f - h.beta1) * gj);
-      V[j] = fmaf(h.beta2, V[j], (1.f - h.beta2) * gj * gj);
-      const float denom = sqrtf(V[j]) * h.inv_sqrt_bc2 + h.eps;
-      P[j] = P[j] - h.step_size * (M[j] / denom);
-    }
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
-    if (pbf) {
-      uint2 o;
-      o.x = pack_bf16x2(pp.x, pp.y);
-      o.y = pack_bf16x2(pp.z, pp.w);
-      reinterpret_cast<uint2*>(pbf)[i] = o;
-    }
-  }
+  arena_body(AdamRule{h, {m, v}}, p, g, pbf, n4);
 }
 
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ buf, uint16_t* __restrict__ pbf,
                                                   int64_t n4, SgdParams h) {
-  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-    float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 bb = buf ? reinterpret_cast<float4*>(buf)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float* P = &pp.x;
-    float* G = &gg.x;
-    float* B = &bb.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float d = G[j];
-      if (h.weight_decay != 0.f) d = fmaf(h.weight_decay, P[j], d);
-      if (buf) {
-        B[j] = h.first_step ? d : fmaf(h.momentum, B[j], (1.f - h.dampening) * d);
-        d = h.nesterov ? fmaf(h.momentum, B[j], d) : B[j];
-      }
-      P[j] = fmaf(-h.lr, d, P[j]);
-    }
-    reinterpret_cast<float4*>(p)[i] = pp;
-    if (buf) reinterpret_cast<float4*>(buf)[i] = bb;
-    if (pbf) {
-      uint2 o;
-      o.x = pack_bf16x2(pp.x, pp.y);
-      o.y = pack_bf16x2(pp.z, pp.w);
-      reinterpret_cast<uint2*>(pbf)[i] = o;
-    }
-  }
+  arena_body(SgdRule{h, {buf}}, p, g, pbf, n4);
 }
 
 void adam_step(float* p, const float* g, float* m, float* v, uint16_t* pbf, int64_t n, const AdamParams& h,
@@ -104,21 +173,6 @@ void sgd_step(float* p, const float* g, float* buf, uint16_t* pbf, int64_t n, co
 // torch.optim does).  Master weights and state stay fp32 flat arenas, so
 // FedAvg / gossip / checkpoints are unchanged.
 // ---------------------------------------------------------------------------
-P2_DEVICE void load_grad4(const void* g, bool bf, int64_t i, float (&o)[4]) {
-  if (bf) {
-    const uint2 u = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(g) + i);
-    o[0] = __uint_as_float(u.x << 16);
-    o[1] = __uint_as_float(u.x & 0xffff0000u);
-    o[2] = __uint_as_float(u.y << 16);
-    o[3] = __uint_as_float(u.y & 0xffff0000u);
-  } else {
-    const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(g) + i);
-    o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
-  }
-}
-P2_DEVICE float load_grad1(const void* g, bool bf, int64_t i) {
-  return bf ? bf16_to_f32(static_cast<const uint16_t*>(g)[i]) : static_cast<const float*>(g)[i];
-}
 
 // Memory position, in a channels-last (O, kh, kw, I) tensor, of logical
 // OIHW element ``i``.  32-bit math: one tensor stays below 2^31 elements.
@@ -148,9 +202,10 @@ P2_DEVICE uint32_t cl_hw(int64_t flags) { return uint32_t((flags >> 32) & 0xFFFF
 // ---- channels-last chunks staged through LDS ---------------------------------
 // A chunk of whole output-channel slabs covers the SAME element range in the
 // OIHW state and in the (O, kh, kw, I) gradient / shadow, only permuted inside
-// each slab.  So every global access can be contiguous: the gradient is read
-// as 8 / 16-byte vectors into LDS (one pad word after every I-run, so the
-// OIHW-order reads that follow -- I-runs apart -- hit distinct banks), the
+// each slab (cl_index_fast of a chunk-local element is its chunk-local
+// channels-last position).  So every global access can be contiguous: the
+// gradient is read as 8 / 16-byte vectors into LDS (one pad word after every
+// I-run, so the OIHW-order reads that follow hit distinct banks), the
 // fp32 state is streamed in OIHW order as 16-byte vectors, and the new bf16
 // weights go back through LDS to 8-byte stores.  The per-element gather /
 // scatter of the fallback path below (2-byte gradient loads and shadow stores
@@ -178,38 +233,15 @@ P2_DEVICE void cl_load_grad(ClStage& st, const void* g, bool gbf, int64_t first,
     for (int e = 0; e < 4; ++e) st.g[q + e] = v[e];
   }
 }
-// channels-last position (within the chunk) of OIHW element i
-P2_DEVICE uint32_t cl_local(uint32_t i, uint32_t C, const FastDivU& per_o, const FastDivU& hw) {
-  const uint32_t o = fdivu(i, per_o), r = i - o * per_o.d, c = fdivu(r, hw), s = r - c * hw.d;
-  return o * per_o.d + s * C + c;
-}
 P2_DEVICE void cl_store_shadow(const ClStage& st, uint16_t* __restrict__ sb, int len) {
   for (int j = threadIdx.x * 4; j < len; j += 1024)
     *reinterpret_cast<uint2*>(sb + j) = *reinterpret_cast<const uint2*>(st.sh + j);
 }
 
-P2_DEVICE void adam_elem(float& p, float g, float& m, float& v, const AdamParams& h) {
-  if (h.weight_decay != 0.f) {
-    if (h.decoupled)
-      p *= (1.f - h.lr * h.weight_decay);
-    else
-      g = fmaf(h.weight_decay, p, g);
-  }
-  m = fmaf(h.beta1, m, (1.f - h.beta1) * g);
-  v = fmaf(h.beta2, v, (1.f - h.beta2) * g * g);
-  p = p - h.step_size * (m / (sqrtf(v) * h.inv_sqrt_bc2 + h.eps));
-}
-
-template <bool FD>
-__global__ __launch_bounds__(256) void adam_mt_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                      float* __restrict__ v, uint16_t* __restrict__ pbf,
-                                                      const MTTensor* __restrict__ tens, const int2* __restrict__ chunks,
-                                                      const uint64_t* __restrict__ gptr, AdamParams h) {
-  if (h.t_dev) {
-    const float t = float(*h.t_dev);
-    h.step_size = h.lr / (1.f - powf(h.beta1, t));
-    h.inv_sqrt_bc2 = rsqrtf(1.f - powf(h.beta2, t));
-  }
+// ---- multi-tensor traversal: one block per chunk-table entry -------------------
+template <bool FD, class Rule>
+P2_DEVICE void mt_body(const Rule& r, float* p, uint16_t* pbf, const MTTensor* tens, const int2* chunks,
+                       const uint64_t* gptr) {
   __shared__ ClStage st;
   const int2 ch = chunks[blockIdx.x];
   const void* g = reinterpret_cast<const void*>(gptr[ch.x]);
@@ -218,34 +250,26 @@ __global__ __launch_bounds__(256) void adam_mt_kernel(float* __restrict__ p, flo
   const bool gbf = T.flags & kMTGradBf16, shadow = (T.flags & kMTShadow) && pbf;
   const int64_t start = ch.y;
   const int64_t len = T.n - start < T.chunk ? T.n - start : T.chunk;
-  const int64_t len4 = len & ~int64_t(3);
-  float* P = p + T.off + start;
-  float* M = m + T.off + start;
-  float* V = v + T.off + start;
-  uint16_t* PB = shadow ? pbf + T.off + start : nullptr;
+  const int64_t base = T.off + start;  // the chunk's first element in p, the state arenas and a plain shadow
+  uint16_t* PB = shadow ? pbf + base : nullptr;
   if ((T.flags & kMTPermCL) && cl_staged(cl_c(T.flags), cl_hw(T.flags), len)) {
     const uint32_t C = cl_c(T.flags), HW = cl_hw(T.flags);
     const FastDivU fpo = make_fastdiv_u(C * HW), fhw = make_fastdiv_u(HW), fc = make_fastdiv_u(C);
     cl_load_grad(st, g, gbf, start, int(len), fc);
     __syncthreads();
     for (int i = threadIdx.x * 4; i < len; i += 1024) {
-      float4 pp = *reinterpret_cast<float4*>(P + i), mm = *reinterpret_cast<float4*>(M + i),
-             vv = *reinterpret_cast<float4*>(V + i);
       uint32_t j[4];
+      float gg[4], pv[4], sv[4][Rule::kStates];
+      load4(r, p, base + i, pv, sv);  // in flight under the index math
 #pragma unroll
-      for (int e = 0; e < 4; ++e) j[e] = cl_local(uint32_t(i + e), C, fpo, fhw);
-      adam_elem(pp.x, st.g[cl_pad(j[0], fc)], mm.x, vv.x, h);
-      adam_elem(pp.y, st.g[cl_pad(j[1], fc)], mm.y, vv.y, h);
-      adam_elem(pp.z, st.g[cl_pad(j[2], fc)], mm.z, vv.z, h);
-      adam_elem(pp.w, st.g[cl_pad(j[3], fc)], mm.w, vv.w, h);
-      *reinterpret_cast<float4*>(P + i) = pp;
-      *reinterpret_cast<float4*>(M + i) = mm;
-      *reinterpret_cast<float4*>(V + i) = vv;
+      for (int e = 0; e < 4; ++e) {
+        j[e] = cl_index_fast(uint32_t(i + e), C, fpo, fhw);
+        gg[e] = st.g[cl_pad(j[e], fc)];
+      }
+      step4(r, p, base + i, gg, pv, sv);
       if (PB) {
-        st.sh[j[0]] = f32_to_bf16(pp.x);
-        st.sh[j[1]] = f32_to_bf16(pp.y);
-        st.sh[j[2]] = f32_to_bf16(pp.z);
-        st.sh[j[3]] = f32_to_bf16(pp.w);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) st.sh[j[e]] = f32_to_bf16(pv[e]);
       }
     }
     if (PB) {
@@ -265,16 +289,14 @@ __global__ __launch_bounds__(256) void adam_mt_kernel(float* __restrict__ p, flo
     // 4 elements per thread in flight (state loads + gradient gathers issued
     // together): one dependent round trip per element made this loop latency-bound
     for (int64_t i0 = threadIdx.x; i0 < len; i0 += 4 * 256) {
-      float pv[4], gv[4], mv[4], vv[4];
+      float pv[4], gv[4], sv[4][Rule::kStates];
       uint32_t j[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int64_t i = i0 + u * 256;
         if (i < len) {
           j[u] = FD ? cl_index_fast(uint32_t(start + i), C, fpo, fhw) : cl_index(uint32_t(start + i), C, HW);
-          pv[u] = P[i];
-          mv[u] = M[i];
-          vv[u] = V[i];
+          load1(r, p, base + i, pv[u], sv[u]);
           gv[u] = load_grad1(g, gbf, j[u]);
         }
       }
@@ -282,60 +304,41 @@ __global__ __launch_bounds__(256) void adam_mt_kernel(float* __restrict__ p, flo
       for (int u = 0; u < 4; ++u) {
         const int64_t i = i0 + u * 256;
         if (i < len) {
-          adam_elem(pv[u], gv[u], mv[u], vv[u], h);
-          P[i] = pv[u];
-          M[i] = mv[u];
-          V[i] = vv[u];
+          r.apply(pv[u], gv[u], sv[u]);
+          store1(r, p, base + i, pv[u], sv[u]);
           if (SB) SB[j[u]] = f32_to_bf16(pv[u]);
         }
       }
     }
     return;
   }
+  // contiguous tensors: 16-byte vectors where the chunk starts on one (always, for arenas laid
+  // out by learning/optim.py: offsets are multiples of 64, chunks of kMTChunk), then a scalar tail
+  const int64_t len4 = (reinterpret_cast<uintptr_t>(p + base) & 15) == 0 ? (len & ~int64_t(3)) : 0;
   for (int64_t i = int64_t(threadIdx.x) * 4; i < len4; i += 256 * 4) {
-    float gg[4];
+    float gg[4], pv[4], sv[4][Rule::kStates];
     load_grad4(g, gbf, start + i, gg);
-    float4 pp = *reinterpret_cast<float4*>(P + i), mm = *reinterpret_cast<float4*>(M + i),
-           vv = *reinterpret_cast<float4*>(V + i);
-    adam_elem(pp.x, gg[0], mm.x, vv.x, h);
-    adam_elem(pp.y, gg[1], mm.y, vv.y, h);
-    adam_elem(pp.z, gg[2], mm.z, vv.z, h);
-    adam_elem(pp.w, gg[3], mm.w, vv.w, h);
-    *reinterpret_cast<float4*>(P + i) = pp;
-    *reinterpret_cast<float4*>(M + i) = mm;
-    *reinterpret_cast<float4*>(V + i) = vv;
-    if (PB) {
-      uint2 o;
-      o.x = pack_bf16x2(pp.x, pp.y);
-      o.y = pack_bf16x2(pp.z, pp.w);
-      *reinterpret_cast<uint2*>(PB + i) = o;
-    }
+    load4(r, p, base + i, pv, sv);
+    step4(r, p, base + i, gg, pv, sv);
+    if (PB) store_bf16x4(PB + i, pv);
   }
   for (int64_t i = len4 + threadIdx.x; i < len; i += 256) {
-    adam_elem(P[i], load_grad1(g, gbf, start + i), M[i], V[i], h);
-    if (PB) PB[i] = f32_to_bf16(P[i]);
+    const float np = step1(r, p, base + i, load_grad1(g, gbf, start + i));
+    if (PB) PB[i] = f32_to_bf16(np);
   }
 }
 
-// register form (a pointer to a local would put the momentum on the stack)
-P2_DEVICE float sgd_regs(float& p, float g, float& b, bool has_b, const SgdParams& h) {
-  if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
-  if (has_b) {
-    b = h.first_step ? g : fmaf(h.momentum, b, (1.f - h.dampening) * g);
-    g = h.nesterov ? fmaf(h.momentum, b, g) : b;
+template <bool FD>
+__global__ __launch_bounds__(256) void adam_mt_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                      float* __restrict__ v, uint16_t* __restrict__ pbf,
+                                                      const MTTensor* __restrict__ tens, const int2* __restrict__ chunks,
+                                                      const uint64_t* __restrict__ gptr, AdamParams h) {
+  if (h.t_dev) {  // graph-replayable steps: the bias corrections of step *t_dev, from the fp32 betas
+    const float t = float(*h.t_dev);
+    h.step_size = h.lr / (1.f - powf(h.beta1, t));
+    h.inv_sqrt_bc2 = rsqrtf(1.f - powf(h.beta2, t));
   }
-  p = fmaf(-h.lr, g, p);
-  return p;
-}
-
-P2_DEVICE float sgd_elem(float& p, float g, float* b, const SgdParams& h) {
-  if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
-  if (b) {
-    *b = h.first_step ? g : fmaf(h.momentum, *b, (1.f - h.dampening) * g);
-    g = h.nesterov ? fmaf(h.momentum, *b, g) : *b;
-  }
-  p = fmaf(-h.lr, g, p);
-  return p;
+  mt_body<FD>(AdamRule{h, {m, v}}, p, pbf, tens, chunks, gptr);
 }
 
 template <bool FD>
@@ -343,102 +346,7 @@ __global__ __launch_bounds__(256) void sgd_mt_kernel(float* __restrict__ p, floa
                                                      uint16_t* __restrict__ pbf, const MTTensor* __restrict__ tens,
                                                      const int2* __restrict__ chunks, const uint64_t* __restrict__ gptr,
                                                      SgdParams h) {
-  __shared__ ClStage st;
-  const int2 ch = chunks[blockIdx.x];
-  const void* g = reinterpret_cast<const void*>(gptr[ch.x]);
-  if (g == nullptr) return;
-  const MTTensor T = tens[ch.x];
-  const bool gbf = T.flags & kMTGradBf16, shadow = (T.flags & kMTShadow) && pbf;
-  const int64_t start = ch.y;
-  const int64_t len = T.n - start < T.chunk ? T.n - start : T.chunk;
-  float* P = p + T.off + start;
-  float* B = buf ? buf + T.off + start : nullptr;
-  uint16_t* PB = shadow ? pbf + T.off + start : nullptr;
-  if ((T.flags & kMTPermCL) && cl_staged(cl_c(T.flags), cl_hw(T.flags), len)) {  // see adam_mt_kernel
-    const uint32_t C = cl_c(T.flags), HW = cl_hw(T.flags);
-    const FastDivU fpo = make_fastdiv_u(C * HW), fhw = make_fastdiv_u(HW), fc = make_fastdiv_u(C);
-    cl_load_grad(st, g, gbf, start, int(len), fc);
-    __syncthreads();
-    for (int i = threadIdx.x * 4; i < len; i += 1024) {
-      float4 pp = *reinterpret_cast<float4*>(P + i);
-      float4 bb = B ? *reinterpret_cast<float4*>(B + i) : float4{0.f, 0.f, 0.f, 0.f};
-      uint32_t j[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) j[e] = cl_local(uint32_t(i + e), C, fpo, fhw);
-      sgd_regs(pp.x, st.g[cl_pad(j[0], fc)], bb.x, B != nullptr, h);
-      sgd_regs(pp.y, st.g[cl_pad(j[1], fc)], bb.y, B != nullptr, h);
-      sgd_regs(pp.z, st.g[cl_pad(j[2], fc)], bb.z, B != nullptr, h);
-      sgd_regs(pp.w, st.g[cl_pad(j[3], fc)], bb.w, B != nullptr, h);
-      *reinterpret_cast<float4*>(P + i) = pp;
-      if (B) *reinterpret_cast<float4*>(B + i) = bb;
-      if (PB) {
-        st.sh[j[0]] = f32_to_bf16(pp.x);
-        st.sh[j[1]] = f32_to_bf16(pp.y);
-        st.sh[j[2]] = f32_to_bf16(pp.z);
-        st.sh[j[3]] = f32_to_bf16(pp.w);
-      }
-    }
-    if (PB) {
-      __syncthreads();
-      cl_store_shadow(st, PB, int(len));
-    }
-    return;
-  }
-  if (T.flags & kMTPermCL) {  // gather path (4 elements per thread in flight, see adam_mt_kernel)
-    const uint32_t C = cl_c(T.flags), HW = cl_hw(T.flags);
-    FastDivU fpo{}, fhw{};
-    if (FD) fpo = make_fastdiv_u(C * HW), fhw = make_fastdiv_u(HW);
-    uint16_t* SB = shadow ? pbf + T.off : nullptr;
-    for (int64_t i0 = threadIdx.x; i0 < len; i0 += 4 * 256) {
-      float pv[4], gv[4], bv[4];
-      uint32_t j[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t i = i0 + u * 256;
-        if (i < len) {
-          j[u] = FD ? cl_index_fast(uint32_t(start + i), C, fpo, fhw) : cl_index(uint32_t(start + i), C, HW);
-          pv[u] = P[i];
-          bv[u] = B ? B[i] : 0.f;
-          gv[u] = load_grad1(g, gbf, j[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t i = i0 + u * 256;
-        if (i < len) {
-          const float np = sgd_regs(pv[u], gv[u], bv[u], B != nullptr, h);
-          P[i] = np;
-          if (B) B[i] = bv[u];
-          if (SB) SB[j[u]] = f32_to_bf16(np);
-        }
-      }
-    }
-    return;
-  }
-  // contiguous tensors: 16-B vectors, as adam_mt_kernel
-  const int64_t len4 = (reinterpret_cast<uintptr_t>(P) & 15) == 0 ? (len & ~int64_t(3)) : 0;
-  for (int64_t i = int64_t(threadIdx.x) * 4; i < len4; i += 256 * 4) {
-    float gg[4];
-    load_grad4(g, gbf, start + i, gg);
-    float4 pp = *reinterpret_cast<float4*>(P + i);
-    float4 bb = B ? *reinterpret_cast<float4*>(B + i) : float4{0.f, 0.f, 0.f, 0.f};
-    sgd_regs(pp.x, gg[0], bb.x, B != nullptr, h);
-    sgd_regs(pp.y, gg[1], bb.y, B != nullptr, h);
-    sgd_regs(pp.z, gg[2], bb.z, B != nullptr, h);
-    sgd_regs(pp.w, gg[3], bb.w, B != nullptr, h);
-    *reinterpret_cast<float4*>(P + i) = pp;
-    if (B) *reinterpret_cast<float4*>(B + i) = bb;
-    if (PB) {
-      uint2 o;
-      o.x = pack_bf16x2(pp.x, pp.y);
-      o.y = pack_bf16x2(pp.z, pp.w);
-      *reinterpret_cast<uint2*>(PB + i) = o;
-    }
-  }
-  for (int64_t i = len4 + threadIdx.x; i < len; i += 256) {
-    const float np = sgd_elem(P[i], load_grad1(g, gbf, start + i), B ? B + i : nullptr, h);
-    if (PB) PB[i] = f32_to_bf16(np);
-  }
+  mt_body<FD>(SgdRule{h, {buf}}, p, pbf, tens, chunks, gptr);
 }
 
 // channels-last index by multiply-high (default) or by integer division (P2_MT_FASTDIV=0; A/B knob, read once)

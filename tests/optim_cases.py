@@ -156,7 +156,7 @@ def host_bias(hp: dict, t: int, from_rounded: bool = True):
 
 
 def adam_emu(p, g, m, v, hp: dict, step_size: float, inv_sqrt_bc2: float, fused: bool) -> dict:
-    """adam_elem of csrc/optim.hip in float32.  The explicit fmaf calls are always fused;
+    """AdamRule::apply of csrc/optim.hip in float32.  The explicit fmaf calls are always fused;
     ``fused`` says whether the compiler also contracted the three a * b + c it is free to
     contract (the decay factor, the denominator and the final update)."""
     h = rounded(hp)
@@ -177,7 +177,7 @@ def adam_emu(p, g, m, v, hp: dict, step_size: float, inv_sqrt_bc2: float, fused:
 
 
 def sgd_emu(p, g, buf, hp: dict) -> dict:
-    """sgd_regs / sgd_elem of csrc/optim.hip in float32: every a * b + c there is an explicit
+    """SgdRule::apply of csrc/optim.hip in float32: every a * b + c there is an explicit
     fmaf, so there is one contraction form only."""
     h = rounded(hp)
     lr, mu, damp, wd = h["lr"], h["momentum"], h["dampening"], h["weight_decay"]

@@ -61,6 +61,9 @@ Measured bitwise claims (MI355X)
   bitwise equal in p, state and shadow -- asserted.
 * ``gtab`` (with 0 entries for skipped tensors, ``grads=[]``) vs the gradient list: bitwise equal --
   asserted.
+* whole-arena kernel on a flat fp32 arena vs multi-tensor kernel on the same values as one dense
+  tensor with an fp32 gradient (n = 1028; Adam coupled and decoupled, SGD Nesterov): p, state and
+  shadow bitwise equal -- asserted (both traversals instantiate the same AdamRule / SgdRule).
 * ``p_bf16=None`` vs a shadow: same p and state bits; the shadow is the kernel's own p rounded to bf16,
   bitwise, at its channels-last positions; padding, unshadowed and skipped regions keep their sentinels.
 
@@ -386,6 +389,31 @@ def test_paths_are_bitwise_equal(opt, name):
                     diff = int((_bits(out[k][oi:oi + n]) != _bits(out[k][o0:o0 + n])).sum())
                     print(f"{opt} {name} {'bf16' if half == 0 else 'fp32'} {oc.kind_of(shapes[i])} vs dense, {k}: {diff} differ")
                     assert diff == 0, (k, shapes[i], diff)
+
+
+@pytest.mark.parametrize("opt,name", [("adam", "adam_wd"), ("adam", "adamw"), ("sgd", "nesterov")])
+def test_arena_and_mt_kernels_are_bitwise_equal(opt, name):
+    """One update rule under both traversals: the whole-arena kernel on a flat fp32 arena and the
+    multi-tensor kernel on the same values as a single dense tensor with an fp32 gradient give
+    bit for bit the same p, state and shadow."""
+    n = 1028  # 257 float4, no scalar tail
+    assert n in NS
+    hp, t = _sets(opt)[name], 2
+    lay = oc.Layout([(n,)], [False], [True]).to(DEV)
+    inp = oc.mt_inputs(lay, "wide", seed=7)
+    mt = oc.run_mt(ops, lay, opt, hp, t, inp, DEV)
+    _check_mt(f"{opt}_mt {name} single dense tensor", lay, opt, hp, t, inp, mt)
+    g = inp["glog"][:n].to(DEV)
+    flat = {k: inp[k][:n].to(DEV) for k in (("p", "m", "v") if opt == "adam" else ("p", "buf"))}
+    shadow = torch.full((n,), oc.SENTINEL["shadow"], dtype=torch.bfloat16, device=DEV)
+    if opt == "adam":
+        ops.adam_step(flat["p"], g, flat["m"], flat["v"], step=t, p_bf16=shadow, **hp)
+    else:
+        assert hp["has_buf"]
+        ops.sgd_step(flat["p"], g, flat["buf"], p_bf16=shadow, **oc.sgd_kwargs(hp))
+    for k, x in flat.items():
+        _same_bits(f"{opt} {name} whole-arena vs multi-tensor: {k}", mt[k][:n], x)
+    _same_bits(f"{opt} {name} whole-arena vs multi-tensor: shadow", mt["shadow"][:n], shadow)
 
 
 @pytest.mark.parametrize("opt,name", [("adam", "adam_wd"), ("sgd", "nesterov")])

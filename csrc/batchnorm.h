@@ -40,10 +40,10 @@ void bn_apply_train(bool bf16, const void* x, const void* res, const float* coef
 void bn_apply_bwd_only(const void* dy, const void* y, const void* x, const float* mean, const float* coef, void* dx,
                        int M, int C, bool relu, hipStream_t s);
 
-// Inference forward with running statistics (one launch; coef unused, kept for
-// the call signature).  w, b, run_mean, run_var must be 16-byte aligned.
+// Inference forward with running statistics (one launch).  w, b, run_mean,
+// run_var must be 16-byte aligned.
 void bn_fwd_eval(bool bf16, const void* x, const void* res, const float* w, const float* b, const float* run_mean,
-                 const float* run_var, float eps, void* y, float* coef, int M, int C, bool relu, hipStream_t s);
+                 const float* run_var, float eps, void* y, int M, int C, bool relu, hipStream_t s);
 
 // Backward of y = act(bn(x) [+ res]) given dy and the saved output y (ReLU mask):
 //   dz = relu ? dy * (y > 0) : dy

@@ -23,49 +23,15 @@
 // standard deviations over 32768 rows).  ReLU and the variance clamp are
 // comparisons, not fmaxf: a NaN or Inf activation gives a NaN channel (mean,
 // rstd, y, running statistics) rather than a finite one.
+#include <type_traits>
+
 #include "batchnorm.h"
 #include "common.h"
 
 namespace p2bn {
 using namespace p2;
 
-template <typename T>
-struct V8;
-template <>
-struct V8<uint16_t> {
-  static P2_DEVICE void load(const uint16_t* p, float (&v)[8]) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  }
-  static P2_DEVICE void store(uint16_t* p, const float (&v)[8]) {
-    uint4 u;
-    u.x = pack_bf16x2(v[0], v[1]);
-    u.y = pack_bf16x2(v[2], v[3]);
-    u.z = pack_bf16x2(v[4], v[5]);
-    u.w = pack_bf16x2(v[6], v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-  }
-  static P2_DEVICE float one(const uint16_t* p) { return bf16_to_f32(*p); }
-};
-template <>
-struct V8<float> {
-  static P2_DEVICE void load(const float* p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  static P2_DEVICE void store(float* p, const float (&v)[8]) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-  static P2_DEVICE float one(const float* p) { return *p; }
-};
-P2_DEVICE void ld8f(const float* p, float (&v)[8]) { V8<float>::load(p, v); }
+P2_DEVICE void ld8f(const float* p, float (&v)[8]) { Vec8<float>::load(p, v); }
 
 constexpr int kThreads = 256;
 constexpr int kRedCols = kThreads * 8;  // LDS columns of one phase-reduction slab
@@ -73,10 +39,17 @@ constexpr int kInFlight = 4;             // rows per thread in flight in the sta
 
 // ---------------------------------------------------------------------------
 // Block-level fixed-order reduction of two per-thread [8] accumulators over
-// the rp row phases, written as row blockIdx.y of the [S, C] partials a / b.
+// the rp row phases, written as row blockIdx.y of the [S, C] partials a / b:
+// st(i, v) stores element i of the [2, S, C] partials.
 // ---------------------------------------------------------------------------
-P2_DEVICE void phase_reduce_store(float (&s1)[8], float (&s2)[8], bool active, int tg, int ph, int tpr, int rp,
-                                  float* __restrict__ part, int C) {
+struct PlainStore {
+  float* __restrict__ part;
+  P2_DEVICE void operator()(size_t i, float v) const { part[i] = v; }
+};
+
+template <class Store>
+P2_DEVICE void phase_reduce_store(const float (&s1)[8], const float (&s2)[8], bool active, int tg, int ph, int tpr,
+                                  int rp, int C, const Store& st) {
   __shared__ float red[2][kRedCols];
   const int width = tpr * 8;  // columns of this block
   if (active) {
@@ -96,8 +69,30 @@ P2_DEVICE void phase_reduce_store(float (&s1)[8], float (&s2)[8], bool active, i
       a += red[0][p * width + i];
       b += red[1][p * width + i];
     }
-    part[size_t(blockIdx.y) * C + c] = a;
-    part[size_t(S + blockIdx.y) * C + c] = b;
+    st(size_t(blockIdx.y) * C + c, a);
+    st(size_t(S + blockIdx.y) * C + c, b);
+  }
+}
+
+// One row's share of the forward sums, d = x - x0 (a row past M counts zero).
+P2_DEVICE void acc_fwd(const float (&v)[8], const float (&sh)[8], bool in, float (&s1)[8], float (&s2)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float d = in ? v[j] - sh[j] : 0.f;
+    s1[j] += d;
+    s2[j] = fmaf(d, d, s2[j]);
+  }
+}
+
+// One row's share of the backward sums, dz = g behind the ReLU mask y > 0 (yv is read only with RELU).
+template <bool RELU>
+P2_DEVICE void acc_bwd(const float (&g)[8], const float (&xv)[8], const float (&yv)[8], const float (&mu)[8], bool in,
+                       float (&s1)[8], float (&s2)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float gg = in && (!RELU || yv[j] > 0.f) ? g[j] : 0.f;
+    s1[j] += gg;
+    s2[j] = fmaf(gg, xv[j] - mu[j], s2[j]);
   }
 }
 
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const T* __restrict_
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
   if (active) {
     float sh[8];
-    V8<T>::load(x + c, sh);
+    Vec8<T>::load(x + c, sh);
     const int step = rp * gridDim.y;
     // kInFlight rows per iteration, loaded unconditionally (rows past M re-read
     // row 0 and count zero): a load under a branch gets its own vmcnt(0), which
@@ -123,21 +118,13 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const T* __restrict_
 #pragma unroll
       for (int u = 0; u < kInFlight; ++u) {
         const int ru = r + u * step;
-        V8<T>::load(x + size_t(ru < M ? ru : 0) * C + c, v[u]);
+        Vec8<T>::load(x + size_t(ru < M ? ru : 0) * C + c, v[u]);
       }
 #pragma unroll
-      for (int u = 0; u < kInFlight; ++u) {
-        const bool in = r + u * step < M;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = in ? v[u][j] - sh[j] : 0.f;
-          s1[j] += d;
-          s2[j] = fmaf(d, d, s2[j]);
-        }
-      }
+      for (int u = 0; u < kInFlight; ++u) acc_fwd(v[u], sh, r + u * step < M, s1, s2);
     }
   }
-  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, part, C);
+  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, C, PlainStore{part});
 }
 
 // backward statistics: sum dz and sum dz * (x - mean) per channel.  dy2 (or null):
@@ -167,33 +154,25 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_stats_kernel(const T* __restr
       for (int u = 0; u < kInFlight; ++u) {
         const int ru = r + u * step;
         const size_t e = size_t(ru < M ? ru : 0) * C + c;
-        V8<T>::load(dy + e, g[u]);
-        V8<T>::load(x + e, xv[u]);
-        if (RELU) V8<T>::load(y + e, yv[u]);
+        Vec8<T>::load(dy + e, g[u]);
+        Vec8<T>::load(x + e, xv[u]);
+        if (RELU) Vec8<T>::load(y + e, yv[u]);
       }
       if (dy2) {
 #pragma unroll
         for (int u = 0; u < kInFlight; ++u) {
           const int ru = r + u * step;
           float g2[8];
-          V8<T>::load(dy2 + size_t(ru < M ? ru : 0) * C + c, g2);
+          Vec8<T>::load(dy2 + size_t(ru < M ? ru : 0) * C + c, g2);
 #pragma unroll
           for (int j = 0; j < 8; ++j) g[u][j] += g2[j];
         }
       }
 #pragma unroll
-      for (int u = 0; u < kInFlight; ++u) {
-        const bool in = r + u * step < M;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float gg = in && (!RELU || yv[u][j] > 0.f) ? g[u][j] : 0.f;
-          s1[j] += gg;
-          s2[j] = fmaf(gg, xv[u][j] - mu[j], s2[j]);
-        }
-      }
+      for (int u = 0; u < kInFlight; ++u) acc_bwd<RELU>(g[u], xv[u], yv[u], mu, r + u * step < M, s1, s2);
     }
   }
-  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, part, C);
+  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, C, PlainStore{part});
 }
 
 // ---------------------------------------------------------------------------
@@ -201,6 +180,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_stats_kernel(const T* __restr
 // thread (two arrays), then a fixed-order sum over the phases in LDS.  The
 // S <= 256 partial rows are read in <= 2 rounds of memory latency (the
 // earlier 64 x 4 split needed up to 16 dependent rounds: 5.5 us per call).
+// Not merged with fused_reduce_parts below (4 columns per thread x pq phases):
+// the two sum the partial rows in different orders, so sharing one would
+// change the bits of the other.
 // ---------------------------------------------------------------------------
 constexpr int kFinCols = 16, kFinPh = kThreads / kFinCols;
 
@@ -238,21 +220,16 @@ P2_DEVICE void reduce_parts(const float* __restrict__ part, int S, int C, int c,
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void bn_finalize_fwd_kernel(
-    const float* __restrict__ part, int S, const T* __restrict__ x, const float* __restrict__ w,
-    const float* __restrict__ b, float* __restrict__ run_mean, float* __restrict__ run_var, int64_t* __restrict__ nbt,
-    float momentum, float eps, float* __restrict__ mean_out, float* __restrict__ rstd_out, float* __restrict__ coef,
-    int M, int C) {
-  const int c = blockIdx.x * kFinCols + (threadIdx.x % kFinCols);
-  float s1, s2;
-  reduce_parts(part, S, C, c, s1, s2);
-  if (threadIdx.x >= kFinCols || c >= C) return;
+// Forward finalize of channel c from its shifted sums s1 = sum (x - x0), s2 = sum (x - x0)^2:
+// mean, rstd, coef = [mean | w rstd | b], running statistics (unbiased variance).
+P2_DEVICE void fin_fwd(int c, float s1, float s2, float x0, const float* w, const float* b, float* run_mean,
+                       float* run_var, float momentum, float eps, float* mean_out, float* rstd_out, float* coef, int M,
+                       int C) {
   const float inv_m = 1.f / float(M);
   const float ms = s1 * inv_m;
   const float v0 = s2 * inv_m - ms * ms;
   const float var = v0 < 0.f ? 0.f : v0;  // a NaN (an Inf or NaN activation) stays a NaN
-  const float mu = V8<T>::one(x + c) + ms;
+  const float mu = x0 + ms;
   const float rs = rsqrtf(var + eps);
   mean_out[c] = mu;
   rstd_out[c] = rs;
@@ -264,11 +241,35 @@ __global__ __launch_bounds__(kThreads) void bn_finalize_fwd_kernel(
     run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mu;
     run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
   }
+}
+
+// Backward finalize of channel c from s1 = sum dz, s2 = sum dz (x - mean):
+// db = s1, dw = rstd s2, coef = [A | B | D] with dx = A dz + B (x - mean) + D
+P2_DEVICE void fin_bwd(int c, float s1, float s2, const float* w, const float* rstd, float* dw, float* db, float* coef,
+                       int M, int C) {
+  const float rs = rstd[c], inv_m = 1.f / float(M);
+  const float A = w[c] * rs;
+  db[c] = s1;
+  dw[c] = s2 * rs;
+  coef[c] = A;
+  coef[C + c] = -A * rs * rs * s2 * inv_m;
+  coef[2 * C + c] = -A * s1 * inv_m;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void bn_finalize_fwd_kernel(
+    const float* __restrict__ part, int S, const T* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ b, float* __restrict__ run_mean, float* __restrict__ run_var, int64_t* __restrict__ nbt,
+    float momentum, float eps, float* __restrict__ mean_out, float* __restrict__ rstd_out, float* __restrict__ coef,
+    int M, int C) {
+  const int c = blockIdx.x * kFinCols + (threadIdx.x % kFinCols);
+  float s1, s2;
+  reduce_parts(part, S, C, c, s1, s2);
+  if (threadIdx.x >= kFinCols || c >= C) return;
+  fin_fwd(c, s1, s2, Vec8<T>::one(x + c), w, b, run_mean, run_var, momentum, eps, mean_out, rstd_out, coef, M, C);
   if (nbt && c == 0) nbt[0] += 1;
 }
 
-
-// coef = [A | B | D]: dx = A dz + B (x - mean) + D;  dw = rstd * s2, db = s1
 __global__ __launch_bounds__(kThreads) void bn_finalize_bwd_kernel(const float* __restrict__ part, int S,
                                                                    const float* __restrict__ w,
                                                                    const float* __restrict__ rstd,
@@ -278,13 +279,7 @@ __global__ __launch_bounds__(kThreads) void bn_finalize_bwd_kernel(const float* 
   float s1, s2;
   reduce_parts(part, S, C, c, s1, s2);
   if (threadIdx.x >= kFinCols || c >= C) return;
-  const float rs = rstd[c], inv_m = 1.f / float(M);
-  const float A = w[c] * rs;
-  db[c] = s1;
-  dw[c] = s2 * rs;
-  coef[c] = A;
-  coef[C + c] = -A * rs * rs * s2 * inv_m;
-  coef[2 * C + c] = -A * s1 * inv_m;
+  fin_bwd(c, s1, s2, w, rstd, dw, db, coef, M, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -303,7 +298,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_fwd_kernel(const T* __restr
     const int64_t e = i * 8;
     const int c = int(e % C);
     float v[8], mu[8], sc[8], bb[8];
-    V8<T>::load(x + e, v);
+    Vec8<T>::load(x + e, v);
     ld8f(c_mean + c, mu);
     ld8f(c_scale + c, sc);
     ld8f(c_bias + c, bb);
@@ -317,7 +312,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_fwd_kernel(const T* __restr
     for (int j = 0; j < 8; ++j) v[j] = fmaf(v[j] - mu[j], sc[j], bb[j]);
     if (RES) {
       float r[8];
-      V8<T>::load(res + e, r);
+      Vec8<T>::load(res + e, r);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] += r[j];
     }
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_fwd_kernel(const T* __restr
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = v[j] < 0.f ? 0.f : v[j];  // not fmaxf: a NaN stays a NaN
     }
-    V8<T>::store(y + e, v);
+    Vec8<T>::store(y + e, v);
   }
 }
 
@@ -340,17 +335,17 @@ __global__ __launch_bounds__(kThreads) void bn_apply_bwd_kernel(const T* __restr
     const int64_t e = i * 8;
     const int c = int(e % C);
     float g[8], xv[8], mu[8], A[8], B[8], D[8];
-    V8<T>::load(dy + e, g);
-    V8<T>::load(x + e, xv);
+    Vec8<T>::load(dy + e, g);
+    Vec8<T>::load(x + e, xv);
     if (dy2) {
       float g2[8];
-      V8<T>::load(dy2 + e, g2);
+      Vec8<T>::load(dy2 + e, g2);
 #pragma unroll
       for (int j = 0; j < 8; ++j) g[j] += g2[j];
     }
     if (RELU) {
       float yv[8];
-      V8<T>::load(y + e, yv);
+      Vec8<T>::load(y + e, yv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) g[j] = yv[j] > 0.f ? g[j] : 0.f;
     }
@@ -358,11 +353,11 @@ __global__ __launch_bounds__(kThreads) void bn_apply_bwd_kernel(const T* __restr
     ld8f(coef + c, A);
     ld8f(coef + C + c, B);
     ld8f(coef + 2 * C + c, D);
-    if (RES) V8<T>::store(dres + e, g);
+    if (RES) Vec8<T>::store(dres + e, g);
     float o[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = fmaf(A[j], g[j], fmaf(B[j], xv[j] - mu[j], D[j]));
-    V8<T>::store(dx + e, o);
+    Vec8<T>::store(dx + e, o);
   }
 }
 
@@ -388,29 +383,13 @@ P2_DEVICE __amdgpu_buffer_rsrc_t f32_rsrc(const float* p, int n) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, n * 4, 0x00020000);
 }
 
-// Block phase reduction of (s1, s2) written as partial row blockIdx.y with sc1 stores.
-P2_DEVICE void fused_partial_store(const float (&s1)[8], const float (&s2)[8], bool active, int tg, int ph, int rp,
-                                   float* part, int S, int C) {
-  __shared__ float red[2][kRedCols];
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[0][ph * C + tg * 8 + j] = s1[j];
-      red[1][ph * C + tg * 8 + j] = s2[j];
-    }
+// phase_reduce_store's store for these kernels: sc1 (write-through) buffer stores
+struct Sc1Store {
+  __amdgpu_buffer_rsrc_t rs;
+  P2_DEVICE void operator()(size_t i, float v) const {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, int(i) * 4, 0, 16);
   }
-  __syncthreads();
-  const auto rs = f32_rsrc(part, 2 * S * C);
-  for (int c = threadIdx.x; c < C; c += kThreads) {
-    float a = 0.f, b = 0.f;
-    for (int p = 0; p < rp; ++p) {
-      a += red[0][p * C + c];
-      b += red[1][p * C + c];
-    }
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a), rs, (blockIdx.y * C + c) * 4, 0, 16);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(b), rs, ((S + blockIdx.y) * C + c) * 4, 0, 16);
-  }
-}
+};
 
 // Ticket: true in the one block that arrived last (every block drained its
 // sc1 partial stores before taking its ticket); it resets the counter.
@@ -476,15 +455,6 @@ P2_DEVICE void fused_reduce_parts(const float* part, int S, int C, Fn&& fn) {
   }
 }
 
-P2_DEVICE void unpack8(const uint4& u, float (&v)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(w[j] << 16);
-    v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-  }
-}
-
 // forward: statistics + finalize (coef / mean / rstd / running stats as bn_finalize_fwd_kernel)
 __global__ __launch_bounds__(kThreads) void bn_stats_fin_kernel(
     const uint16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
@@ -499,7 +469,7 @@ __global__ __launch_bounds__(kThreads) void bn_stats_fin_kernel(
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
   if (active) {
     float sh[8];
-    V8<uint16_t>::load(x + c, sh);
+    Vec8<uint16_t>::load(x + c, sh);
     uint4 xv[kFuseRows];
 #pragma unroll
     for (int k = 0; k < kFuseRows; ++k) {
@@ -508,40 +478,18 @@ __global__ __launch_bounds__(kThreads) void bn_stats_fin_kernel(
     }
 #pragma unroll
     for (int k = 0; k < kFuseRows; ++k) {
-      if (r0 + k * rp >= M) continue;
       float v[8];
-      unpack8(xv[k], v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = v[j] - sh[j];
-        s1[j] += d;
-        s2[j] = fmaf(d, d, s2[j]);
-      }
+      Vec8<uint16_t>::unpack(xv[k], v);
+      acc_fwd(v, sh, r0 + k * rp < M, s1, s2);
     }
   }
-  fused_partial_store(s1, s2, active, tg, ph, rp, part, S, C);
+  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, C, Sc1Store{f32_rsrc(part, 2 * S * C)});
   if (!fused_arrive(ctr, S)) return;
-  const float inv_m = 1.f / float(M);
   fused_reduce_parts(part, S, C, [&](int c0, const f32x4& sa, const f32x4& sb) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int cc = c0 + e;
-      const float ms = sa[e] * inv_m;
-      const float v0 = sb[e] * inv_m - ms * ms;
-      const float var = v0 < 0.f ? 0.f : v0;  // NaN stays NaN
-      const float mu = bf16_to_f32(x[cc]) + ms;
-      const float rsd = rsqrtf(var + eps);
-      mean_out[cc] = mu;
-      rstd_out[cc] = rsd;
-      coef[cc] = mu;
-      coef[C + cc] = w[cc] * rsd;
-      coef[2 * C + cc] = b[cc];
-      if (run_mean) {
-        const float unb = M > 1 ? var * (float(M) / float(M - 1)) : var;
-        run_mean[cc] = (1.f - momentum) * run_mean[cc] + momentum * mu;
-        run_var[cc] = (1.f - momentum) * run_var[cc] + momentum * unb;
-      }
-    }
+    for (int e = 0; e < 4; ++e)
+      fin_fwd(c0 + e, sa[e], sb[e], Vec8<uint16_t>::one(x + c0 + e), w, b, run_mean, run_var, momentum, eps, mean_out,
+              rstd_out, coef, M, C);
   });
   if (nbt && threadIdx.x == 0) nbt[0] += 1;
 }
@@ -573,36 +521,18 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_stats_fin_kernel(
     }
 #pragma unroll
     for (int k = 0; k < kFuseRows; ++k) {
-      float g[8], xf[8];
-      unpack8(gv[k], g);
-      unpack8(xv[k], xf);
-      if (RELU) {
-        float yf[8];
-        unpack8(yv[k], yf);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g[j] = yf[j] > 0.f ? g[j] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s1[j] += g[j];
-        s2[j] = fmaf(g[j], xf[j] - mu[j], s2[j]);
-      }
+      float g[8], xf[8], yf[8];
+      Vec8<uint16_t>::unpack(gv[k], g);
+      Vec8<uint16_t>::unpack(xv[k], xf);
+      if (RELU) Vec8<uint16_t>::unpack(yv[k], yf);
+      acc_bwd<RELU>(g, xf, yf, mu, r0 + k * rp < M, s1, s2);
     }
   }
-  fused_partial_store(s1, s2, active, tg, ph, rp, part, S, C);
+  phase_reduce_store(s1, s2, active, tg, ph, tpr, rp, C, Sc1Store{f32_rsrc(part, 2 * S * C)});
   if (!fused_arrive(ctr, S)) return;
-  const float inv_m = 1.f / float(M);
   fused_reduce_parts(part, S, C, [&](int c0, const f32x4& sa, const f32x4& sb) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int cc = c0 + e;
-      const float rsd = rstd[cc], A = w[cc] * rsd;
-      db[cc] = sa[e];
-      dw[cc] = sb[e] * rsd;
-      coef[cc] = A;
-      coef[C + cc] = -A * rsd * rsd * sb[e] * inv_m;
-      coef[2 * C + cc] = -A * sa[e] * inv_m;
-    }
+    for (int e = 0; e < 4; ++e) fin_bwd(c0 + e, sa[e], sb[e], w, rstd, dw, db, coef, M, C);
   });
 }
 
@@ -636,149 +566,122 @@ BnPlan bn_plan(int M, int C) {
   return p;
 }
 
+// Runtime flags as template booleans: fn receives std::true_type / std::false_type values.
+template <class Fn>
+static void with_flag(bool a, Fn&& fn) {
+  a ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <class Fn>
+static void with_flags(bool a, bool b, Fn&& fn) {
+  with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { fn(A, B); }); });
+}
+// fn receives a value of the activation's element type
+template <class Fn>
+static void with_dtype(bool bf16, Fn&& fn) {
+  bf16 ? fn(uint16_t{}) : fn(float{});
+}
+
+constexpr dim3 kBlock(kThreads);
+static dim3 fin_grid(int C) { return dim3((C + kFinCols - 1) / kFinCols); }
+
+// training: (mean, scale, bias) = the finalize kernel's coefficient rows, run_var null;
+// inference: (running_mean, weight, bias) and run_var
 template <typename T>
-static void apply_fwd(const T* x, const T* r, const float* coef, T* y, int M, int C, bool relu, hipStream_t s) {
+static void apply_fwd(const T* x, const T* r, const float* mean, const float* scale, const float* bias,
+                      const float* run_var, float eps, T* y, int M, int C, bool relu, hipStream_t s) {
   const int64_t n8 = int64_t(M) * C / 8;
-  const dim3 grid(stream_grid(n8, kThreads)), blk(kThreads);
-  if (relu && r)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, true, true>), grid, blk, 0, s, x, r, coef, coef + C, coef + 2 * C, nullptr, 0.f, y, n8, C);
-  else if (relu)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, true, false>), grid, blk, 0, s, x, r, coef, coef + C, coef + 2 * C, nullptr, 0.f, y, n8, C);
-  else if (r)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, false, true>), grid, blk, 0, s, x, r, coef, coef + C, coef + 2 * C, nullptr, 0.f, y, n8, C);
-  else
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, false, false>), grid, blk, 0, s, x, r, coef, coef + C, coef + 2 * C, nullptr, 0.f, y, n8, C);
+  with_flags(relu, r != nullptr, [&](auto RELU, auto RES) {
+    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, RELU.value, RES.value>), dim3(stream_grid(n8, kThreads)), kBlock, 0, s, x, r,
+                       mean, scale, bias, run_var, eps, y, n8, C);
+  });
 }
 
 template <typename T>
 static void apply_bwd(const T* dy, const T* dy2, const T* y, const T* x, const float* mean, const float* coef, T* dx,
                       T* dres, int M, int C, bool relu, hipStream_t s) {
   const int64_t n8 = int64_t(M) * C / 8;
-  const dim3 grid(stream_grid(n8, kThreads)), blk(kThreads);
-  if (relu && dres)
-    hipLaunchKernelGGL((bn_apply_bwd_kernel<T, true, true>), grid, blk, 0, s, dy, dy2, y, x, mean, coef, dx, dres, n8, C);
-  else if (relu)
-    hipLaunchKernelGGL((bn_apply_bwd_kernel<T, true, false>), grid, blk, 0, s, dy, dy2, y, x, mean, coef, dx, dres, n8, C);
-  else if (dres)
-    hipLaunchKernelGGL((bn_apply_bwd_kernel<T, false, true>), grid, blk, 0, s, dy, dy2, y, x, mean, coef, dx, dres, n8, C);
-  else
-    hipLaunchKernelGGL((bn_apply_bwd_kernel<T, false, false>), grid, blk, 0, s, dy, dy2, y, x, mean, coef, dx, dres, n8, C);
+  with_flags(relu, dres != nullptr, [&](auto RELU, auto RES) {
+    hipLaunchKernelGGL((bn_apply_bwd_kernel<T, RELU.value, RES.value>), dim3(stream_grid(n8, kThreads)), kBlock, 0, s, dy,
+                       dy2, y, x, mean, coef, dx, dres, n8, C);
+  });
 }
 
-template <typename T>
-static void fwd_train_t(const void* xv, const void* rv, const float* w, const float* b, float* rm, float* rvar,
-                        int64_t* nbt, float momentum, float eps, void* yv, float* mean, float* rstd, float* coef,
-                        float* part, int* ctr, int M, int C, bool relu, hipStream_t s) {
-  const T* x = static_cast<const T*>(xv);
-  const T* r = static_cast<const T*>(rv);
-  T* y = static_cast<T*>(yv);
-  if constexpr (sizeof(T) == 2) {
-    const BnPlan f = bn_fused_plan(M, C);
-    if (ctr && f.S > 0) {
-      hipLaunchKernelGGL(bn_stats_fin_kernel, dim3(1, f.S), dim3(kThreads), 0, s, x, w, b, rm, rvar, nbt, momentum, eps,
-                         mean, rstd, coef, part, ctr, M, C, f.tpr, f.rp);
-      apply_fwd(x, r, coef, y, M, C, relu, s);
-      return;
-    }
-  }
-  const BnPlan p = bn_plan(M, C);
-  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(p.gx, p.S), dim3(kThreads), 0, s, x, part, M, C, p.tpr, p.rp);
-  hipLaunchKernelGGL(bn_finalize_fwd_kernel<T>, dim3((C + kFinCols - 1) / kFinCols), dim3(kThreads), 0, s, part, p.S, x, w, b, rm,
-                     rvar, nbt, momentum, eps, mean, rstd, coef, M, C);
-  apply_fwd(x, r, coef, y, M, C, relu, s);
-}
-
-void bn_fwd_train(bool bf16, const void* x, const void* res, const float* w, const float* b, float* run_mean,
-                  float* run_var, int64_t* nbt, float momentum, float eps, void* y, float* mean, float* rstd,
+void bn_fwd_train(bool bf16, const void* xv, const void* res, const float* w, const float* b, float* run_mean,
+                  float* run_var, int64_t* nbt, float momentum, float eps, void* yv, float* mean, float* rstd,
                   float* coef, float* part, int* ctr, int M, int C, bool relu, hipStream_t s) {
-  if (bf16)
-    fwd_train_t<uint16_t>(x, res, w, b, run_mean, run_var, nbt, momentum, eps, y, mean, rstd, coef, part, ctr, M, C, relu, s);
-  else
-    fwd_train_t<float>(x, res, w, b, run_mean, run_var, nbt, momentum, eps, y, mean, rstd, coef, part, nullptr, M, C, relu, s);
-}
-
-template <typename T>
-static void fwd_eval_t(const void* xv, const void* rv, const float* w, const float* b, const float* rm,
-                       const float* rvar, float eps, void* yv, float* coef, int M, int C, bool relu, hipStream_t s) {
-  const T* x = static_cast<const T*>(xv);
-  const T* r = static_cast<const T*>(rv);
-  T* y = static_cast<T*>(yv);
-  const int64_t n8 = int64_t(M) * C / 8;
-  const dim3 grid(stream_grid(n8, kThreads)), blk(kThreads);
-  if (relu && r)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, true, true>), grid, blk, 0, s, x, r, rm, w, b, rvar, eps, y, n8, C);
-  else if (relu)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, true, false>), grid, blk, 0, s, x, r, rm, w, b, rvar, eps, y, n8, C);
-  else if (r)
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, false, true>), grid, blk, 0, s, x, r, rm, w, b, rvar, eps, y, n8, C);
-  else
-    hipLaunchKernelGGL((bn_apply_fwd_kernel<T, false, false>), grid, blk, 0, s, x, r, rm, w, b, rvar, eps, y, n8, C);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    const T* x = static_cast<const T*>(xv);
+    bool one_launch = false;
+    if constexpr (sizeof(T) == 2) {
+      const BnPlan f = bn_fused_plan(M, C);
+      one_launch = ctr && f.S > 0;
+      if (one_launch)
+        hipLaunchKernelGGL(bn_stats_fin_kernel, dim3(1, f.S), kBlock, 0, s, x, w, b, run_mean, run_var, nbt, momentum, eps,
+                           mean, rstd, coef, part, ctr, M, C, f.tpr, f.rp);
+    }
+    if (!one_launch) {
+      const BnPlan p = bn_plan(M, C);
+      hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(p.gx, p.S), kBlock, 0, s, x, part, M, C, p.tpr, p.rp);
+      hipLaunchKernelGGL(bn_finalize_fwd_kernel<T>, fin_grid(C), kBlock, 0, s, part, p.S, x, w, b, run_mean, run_var, nbt,
+                         momentum, eps, mean, rstd, coef, M, C);
+    }
+    apply_fwd(x, static_cast<const T*>(res), coef, coef + C, coef + 2 * C, nullptr, 0.f, static_cast<T*>(yv), M, C, relu, s);
+  });
 }
 
 void bn_apply_train(bool bf16, const void* x, const void* res, const float* coef, void* y, int M, int C, bool relu,
                     hipStream_t s) {
-  if (bf16)
-    apply_fwd<uint16_t>(static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(res), coef, static_cast<uint16_t*>(y),
-                        M, C, relu, s);
-  else
-    apply_fwd<float>(static_cast<const float*>(x), static_cast<const float*>(res), coef, static_cast<float*>(y), M, C,
-                     relu, s);
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    apply_fwd(static_cast<const T*>(x), static_cast<const T*>(res), coef, coef + C, coef + 2 * C, nullptr, 0.f,
+              static_cast<T*>(y), M, C, relu, s);
+  });
+}
+
+void bn_fwd_eval(bool bf16, const void* x, const void* res, const float* w, const float* b, const float* run_mean,
+                 const float* run_var, float eps, void* y, int M, int C, bool relu, hipStream_t s) {
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    apply_fwd(static_cast<const T*>(x), static_cast<const T*>(res), run_mean, w, b, run_var, eps, static_cast<T*>(y), M, C,
+              relu, s);
+  });
 }
 
 void bn_apply_bwd_only(const void* dy, const void* y, const void* x, const float* mean, const float* coef, void* dx,
                        int M, int C, bool relu, hipStream_t s) {
-  apply_bwd<uint16_t>(static_cast<const uint16_t*>(dy), nullptr, static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(x),
-                      mean, coef, static_cast<uint16_t*>(dx), nullptr, M, C, relu, s);
+  using T = uint16_t;
+  apply_bwd<T>(static_cast<const T*>(dy), nullptr, static_cast<const T*>(y), static_cast<const T*>(x), mean, coef,
+               static_cast<T*>(dx), nullptr, M, C, relu, s);
 }
 
-void bn_fwd_eval(bool bf16, const void* x, const void* res, const float* w, const float* b, const float* run_mean,
-                 const float* run_var, float eps, void* y, float* coef, int M, int C, bool relu, hipStream_t s) {
-  if (bf16)
-    fwd_eval_t<uint16_t>(x, res, w, b, run_mean, run_var, eps, y, coef, M, C, relu, s);
-  else
-    fwd_eval_t<float>(x, res, w, b, run_mean, run_var, eps, y, coef, M, C, relu, s);
-}
-
-template <typename T>
-static void bwd_t(const void* dyv, const void* dy2v, const void* yv, const void* xv, const float* w, const float* mean,
-                  const float* rstd, void* dxv, void* dresv, float* dw, float* db, float* coef, float* part, int* ctr,
-                  int M, int C, bool relu, hipStream_t s) {
-  const T* dy = static_cast<const T*>(dyv);
-  const T* dy2 = static_cast<const T*>(dy2v);
-  const T* y = static_cast<const T*>(yv);
-  const T* x = static_cast<const T*>(xv);
-  T* dx = static_cast<T*>(dxv);
-  T* dres = static_cast<T*>(dresv);
-  if constexpr (sizeof(T) == 2) {
-    const BnPlan f = bn_fused_plan(M, C);
-    if (ctr && f.S > 0 && !dy2) {
-      if (relu)
-        hipLaunchKernelGGL(bn_bwd_stats_fin_kernel<true>, dim3(1, f.S), dim3(kThreads), 0, s, dy, y, x, w, mean, rstd, dw,
-                           db, coef, part, ctr, M, C, f.tpr, f.rp);
-      else
-        hipLaunchKernelGGL(bn_bwd_stats_fin_kernel<false>, dim3(1, f.S), dim3(kThreads), 0, s, dy, y, x, w, mean, rstd, dw,
-                           db, coef, part, ctr, M, C, f.tpr, f.rp);
-      apply_bwd(dy, dy2, y, x, mean, coef, dx, dres, M, C, relu, s);
-      return;
+void bn_bwd(bool bf16, const void* dyv, const void* dy2v, const void* yv, const void* xv, const float* w,
+            const float* mean, const float* rstd, void* dx, void* dres, float* dw, float* db, float* coef, float* part,
+            int* ctr, int M, int C, bool relu, hipStream_t s) {
+  with_dtype(bf16, [&](auto t) {
+    using T = decltype(t);
+    const T *dy = static_cast<const T*>(dyv), *dy2 = static_cast<const T*>(dy2v);
+    const T *y = static_cast<const T*>(yv), *x = static_cast<const T*>(xv);
+    bool one_launch = false;
+    if constexpr (sizeof(T) == 2) {
+      const BnPlan f = bn_fused_plan(M, C);
+      one_launch = ctr && f.S > 0 && !dy2;
+      if (one_launch)
+        with_flag(relu, [&](auto RELU) {
+          hipLaunchKernelGGL(bn_bwd_stats_fin_kernel<RELU.value>, dim3(1, f.S), kBlock, 0, s, dy, y, x, w, mean, rstd, dw,
+                             db, coef, part, ctr, M, C, f.tpr, f.rp);
+        });
     }
-  }
-  const BnPlan p = bn_plan(M, C);
-  const dim3 sgrid(p.gx, p.S), blk(kThreads);
-  if (relu)
-    hipLaunchKernelGGL((bn_bwd_stats_kernel<T, true>), sgrid, blk, 0, s, dy, dy2, y, x, mean, part, M, C, p.tpr, p.rp);
-  else
-    hipLaunchKernelGGL((bn_bwd_stats_kernel<T, false>), sgrid, blk, 0, s, dy, dy2, y, x, mean, part, M, C, p.tpr, p.rp);
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3((C + kFinCols - 1) / kFinCols), blk, 0, s, part, p.S, w, rstd, dw, db, coef, M, C);
-  apply_bwd(dy, dy2, y, x, mean, coef, dx, dres, M, C, relu, s);
-}
-
-void bn_bwd(bool bf16, const void* dy, const void* dy2, const void* y, const void* x, const float* w, const float* mean,
-            const float* rstd, void* dx, void* dres, float* dw, float* db, float* coef, float* part, int* ctr, int M,
-            int C, bool relu, hipStream_t s) {
-  if (bf16)
-    bwd_t<uint16_t>(dy, dy2, y, x, w, mean, rstd, dx, dres, dw, db, coef, part, ctr, M, C, relu, s);
-  else
-    bwd_t<float>(dy, dy2, y, x, w, mean, rstd, dx, dres, dw, db, coef, part, nullptr, M, C, relu, s);
+    if (!one_launch) {
+      const BnPlan p = bn_plan(M, C);
+      with_flag(relu, [&](auto RELU) {
+        hipLaunchKernelGGL((bn_bwd_stats_kernel<T, RELU.value>), dim3(p.gx, p.S), kBlock, 0, s, dy, dy2, y, x, mean, part,
+                           M, C, p.tpr, p.rp);
+      });
+      hipLaunchKernelGGL(bn_finalize_bwd_kernel, fin_grid(C), kBlock, 0, s, part, p.S, w, rstd, dw, db, coef, M, C);
+    }
+    apply_bwd(dy, dy2, y, x, mean, coef, static_cast<T*>(dx), static_cast<T*>(dres), M, C, relu, s);
+  });
 }
 
 }  // namespace p2bn

@@ -30,6 +30,21 @@ float* opt_f32(const c10::optional<torch::Tensor>& t, int64_t C, const torch::Te
   return f32(*t, C, x, name);
 }
 
+// checked pointer of the optional residual (an activation like x), or null
+const void* opt_residual(const c10::optional<torch::Tensor>& t, const torch::Tensor& x) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  act(*t, x, "residual");
+  return t->data_ptr();
+}
+
+// coefficient rows of the apply passes
+float* coef3(const torch::Tensor& coef, int64_t C, const torch::Tensor& x) {
+  TORCH_CHECK(coef.device() == x.device() && coef.is_contiguous() && coef.scalar_type() == torch::kFloat32 &&
+                  coef.numel() == 3 * C,
+              "coef must be a contiguous fp32 [3, C] tensor on x's device");
+  return coef.data_ptr<float>();
+}
+
 // zeroed int32 arrival counter of the statistics + finalize kernels (ops/splitk.py ring), or null
 int* opt_ctr(const c10::optional<torch::Tensor>& t, const torch::Tensor& x) {
   if (!t.has_value() || !t->defined()) return nullptr;
@@ -63,11 +78,7 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor w, torch:
   check_shape(x);
   const int64_t M = x.size(0), C = x.size(1);
   const bool bf = act(x, x, "x");
-  const void* rp = nullptr;
-  if (residual.has_value() && residual->defined()) {
-    act(*residual, x, "residual");
-    rp = residual->data_ptr();
-  }
+  const void* rp = opt_residual(residual, x);
   float* rm = opt_f32(running_mean, C, x, "running_mean");
   float* rv = opt_f32(running_var, C, x, "running_var");
   TORCH_CHECK((rm == nullptr) == (rv == nullptr), "running_mean and running_var go together");
@@ -95,16 +106,9 @@ torch::Tensor bn_apply_train(torch::Tensor x, c10::optional<torch::Tensor> resid
   check_shape(x);
   const int64_t M = x.size(0), C = x.size(1);
   const bool bf = act(x, x, "x");
-  const void* rp = nullptr;
-  if (residual.has_value() && residual->defined()) {
-    act(*residual, x, "residual");
-    rp = residual->data_ptr();
-  }
-  TORCH_CHECK(coef.device() == x.device() && coef.is_contiguous() && coef.scalar_type() == torch::kFloat32 &&
-                  coef.numel() == 3 * C,
-              "coef must be a contiguous fp32 [3, C] tensor on x's device");
+  const void* rp = opt_residual(residual, x);
   auto y = torch::empty_like(x);
-  p2bn::bn_apply_train(bf, x.data_ptr(), rp, coef.data_ptr<float>(), y.data_ptr(), int(M), int(C), relu, stream());
+  p2bn::bn_apply_train(bf, x.data_ptr(), rp, coef3(coef, C, x), y.data_ptr(), int(M), int(C), relu, stream());
   return y;
 }
 
@@ -118,12 +122,10 @@ torch::Tensor bn_apply_bwd(torch::Tensor dy, c10::optional<torch::Tensor> y, tor
   act(dy, x, "dy");
   const bool relu = y.has_value() && y->defined();
   if (relu) act(*y, x, "y");
-  TORCH_CHECK(coef.device() == x.device() && coef.is_contiguous() && coef.scalar_type() == torch::kFloat32 &&
-                  coef.numel() == 3 * C,
-              "coef must be a contiguous fp32 [3, C] tensor on x's device");
+  const float* cf = coef3(coef, C, x);
   auto dx = torch::empty_like(x);
   p2bn::bn_apply_bwd_only(dy.data_ptr(), relu ? y->data_ptr() : nullptr, x.data_ptr(), f32(mean, C, x, "mean"),
-                          coef.data_ptr<float>(), dx.data_ptr(), int(M), int(C), relu, stream());
+                          cf, dx.data_ptr(), int(M), int(C), relu, stream());
   return dx;
 }
 
@@ -133,18 +135,13 @@ torch::Tensor bn_fwd_eval(torch::Tensor x, torch::Tensor w, torch::Tensor b, c10
   check_shape(x);
   const int64_t M = x.size(0), C = x.size(1);
   const bool bf = act(x, x, "x");
-  const void* rp = nullptr;
-  if (residual.has_value() && residual->defined()) {
-    act(*residual, x, "residual");
-    rp = residual->data_ptr();
-  }
+  const void* rp = opt_residual(residual, x);
   for (const auto* t : {&w, &b, &running_mean, &running_var})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "eval BN parameters must be 16-byte aligned");
   auto y = torch::empty_like(x);
-  auto coef = torch::empty({3, C}, x.options().dtype(torch::kFloat32));
   p2bn::bn_fwd_eval(bf, x.data_ptr(), rp, f32(w, C, x, "weight"), f32(b, C, x, "bias"),
                     f32(running_mean, C, x, "running_mean"), f32(running_var, C, x, "running_var"), float(eps),
-                    y.data_ptr(), coef.data_ptr<float>(), int(M), int(C), relu, stream());
+                    y.data_ptr(), int(M), int(C), relu, stream());
   return y;
 }
 

@@ -40,6 +40,44 @@ P2_DEVICE uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// 8 consecutive elements of a bf16 (one 16-B access) or fp32 (two) tensor as floats
+template <typename T>
+struct Vec8;
+template <>
+struct Vec8<uint16_t> {
+  static P2_DEVICE void unpack(const uint4& u, float (&v)[8]) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[2 * j] = __uint_as_float(w[j] << 16);
+      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+    }
+  }
+  static P2_DEVICE void load(const uint16_t* p, float (&v)[8]) { unpack(*reinterpret_cast<const uint4*>(p), v); }
+  static P2_DEVICE void store(uint16_t* p, const float (&v)[8]) {
+    uint4 u;
+    u.x = pack_bf16x2(v[0], v[1]);
+    u.y = pack_bf16x2(v[2], v[3]);
+    u.z = pack_bf16x2(v[4], v[5]);
+    u.w = pack_bf16x2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(p) = u;
+  }
+  static P2_DEVICE float one(const uint16_t* p) { return bf16_to_f32(*p); }
+};
+template <>
+struct Vec8<float> {
+  static P2_DEVICE void load(const float* p, float (&v)[8]) {
+    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  static P2_DEVICE void store(float* p, const float (&v)[8]) {
+    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  static P2_DEVICE float one(const float* p) { return *p; }
+};
+
 // Grid size for a grid-stride memory-bound kernel: enough blocks to cover the
 // 256 CUs several times over, capped (Guideline 11).
 inline int stream_grid(int64_t work_items, int block) {

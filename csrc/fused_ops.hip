@@ -13,41 +13,6 @@
 namespace p2fused {
 using namespace p2;
 
-// ---- 8-element vector load/store for bf16 (16 B) and fp32 (2 x 16 B) ----
-template <typename T>
-struct Vec8;
-template <>
-struct Vec8<uint16_t> {
-  static P2_DEVICE void load(const uint16_t* p, float (&v)[8]) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  }
-  static P2_DEVICE void store(uint16_t* p, const float (&v)[8]) {
-    uint4 u;
-    u.x = pack_bf16x2(v[0], v[1]);
-    u.y = pack_bf16x2(v[2], v[3]);
-    u.z = pack_bf16x2(v[4], v[5]);
-    u.w = pack_bf16x2(v[6], v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-  }
-};
-template <>
-struct Vec8<float> {
-  static P2_DEVICE void load(const float* p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  static P2_DEVICE void store(float* p, const float (&v)[8]) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-};
 P2_DEVICE void load8f(const float* p, float (&v)[8]) { Vec8<float>::load(p, v); }
 // round fp32 values to what a T tensor holds (bf16: RNE; fp32: identity)
 template <typename T>

@@ -283,6 +283,20 @@ def test_apply_from_given_coefficients(M, C, dtype):
                   bc.K_APPLY_DX, op="apply_dx")
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("has_res,relu", COMBOS)
+@pytest.mark.parametrize("M,C", [(129, 24), (2, 8)])
+def test_training_and_given_coefficient_applies_are_bitwise_equal(M, C, has_res, relu, dtype):
+    """The y of bn.fwd_train and bn.apply_train from [mean | w rstd | b] built from that call's own mean and rstd
+    are the same bits: the kernel's scale row is the single fp32 product w[c] * rs, as torch's is, and the
+    training, given-coefficient and inference applies share one launcher and one kernel body."""
+    (x, res, _, _), (w, b, _, _) = _inputs(M, C, "standard", dtype)
+    r = res if has_res else None
+    y, mean, rstd = bx().fwd_train(x, w, b, r, None, None, None, 0.1, 1e-5, relu, None)
+    _same_bits(f"apply_train vs fwd_train {M}x{C} res={has_res} relu={relu}",
+               bx().apply_train(x, r, torch.stack([mean, w * rstd, b]), relu), y)
+
+
 def _eval(label, M, C, dtype, fam="standard"):
     (x, res, _, _), (w, b, rm, rv) = _inputs(M, C, fam, dtype)
     assert float(w[1]) == 0 and float(w[2]) < 0

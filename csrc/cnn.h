@@ -12,7 +12,8 @@
 //                      operands streamed from L2, bias + ReLU + maxpool epilogue -> A1 + argmax
 //  3 gemm_skinny       FC1: [B x 3136] x [3136 x 2048], split-K fp32 slabs
 //  4 head              slab reduce + bias + ReLU -> H; FC2; softmax-xent; dlogits;
-//                      dH = relu'(H) * dlogits W2; loss/accuracy stats
+//                      dH = relu'(H) * dlogits W2; loss/accuracy stats; one extra
+//                      workgroup leaves Adam's two step scalars for 5-8 (AdamCfg::scal)
 //  5 route_fc2         dA1 = dH x W1 (W1^T bf16 shadow) + pool2/ReLU backward in
 //                      the epilogue -> dC2 map + fp32 bias terms;  extra blocks:
 //                      dW2 = dlogits^T H and db2 with Adam applied in place
@@ -61,8 +62,13 @@ bool xcd_align();
 // (*adam_t + t_off): the host sets the base once per epoch and each captured
 // step bakes in its own offset, so a whole epoch replays as one HIP graph
 // with no per-step counter kernel.
+// scal (may be null): the step's two scalars {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)},
+// written by the step's training head launch (head's step_scal); an Adam role reads
+// them from there instead of computing them in every thread (cnn_adam_dev.h).  It is
+// device memory rewritten every step, never a value fixed when a graph is captured.
 struct AdamCfg {
   float lr, beta1, beta2, eps, weight_decay;
+  const float* scal;
 };
 
 // Arena offsets (elements) of every parameter, from ParamLayout.
@@ -103,9 +109,16 @@ void fc1_eval(const uint16_t* A, const uint16_t* W1bf, float* slabs, int mrows, 
 // w2bf non-null: the FC2 weight is read from its bf16 copy [10][2048] (half the
 // bytes of the fp32 master) -- kept current by fc1_conv_adam / pack_shadows.
 // train = 0 (evaluation): B workgroups, no dH, and dlogits receives the logits themselves
+// step_scal non-null (training launches only): one lane of an extra workgroup also writes
+// Adam's scalars at step (*adam_t + t_off) there, 2 floats, for the step's Adam roles
+// (AdamCfg::scal); cfg.scal is not read.  An evaluation launch never writes them.
 void head(const float* slabs, int S, int mrows, const float* params, Offsets off, const int64_t* labels,
           const int64_t* idx, int B, int train, uint16_t* H, uint16_t* dH, float* dlogits, float* stats,
-          const uint16_t* w2bf, hipStream_t s);
+          const uint16_t* w2bf, float* step_scal, const int* adam_t, int t_off, AdamCfg cfg, hipStream_t s);
+
+// The scalars as an Adam role computes them inline, one lane per step: those of steps
+// (*adam_t + t_off + i), i in [0, n), -> out[2 i], out[2 i + 1] (tests)
+void adam_scal_probe(const int* adam_t, int t_off, AdamCfg cfg, float* out, int n, hipStream_t s);
 
 void fc1_wgrad_adam(const uint16_t* dH, const uint16_t* a1, int mrows, float* params, float* m, float* v,
                     float* gdump, uint16_t* w1bf, uint16_t* w1tbf, Offsets off, const int* adam_t, int t_off,

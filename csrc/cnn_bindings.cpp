@@ -146,10 +146,20 @@ void k_gemm_skinny(torch::Tensor A, torch::Tensor Bt, torch::Tensor slabs, int64
                      stream());
 }
 
+AdamCfg cfg(double lr, double b1, double b2, double eps, double wd,
+            const c10::optional<torch::Tensor>& scal = c10::nullopt);
+
+// step_scal (training launches): the buffer that receives Adam's scalars of step
+// adam_t[0] + t_off for the step's Adam launches; needs adam_t and lr / b1 / b2
 void k_head(torch::Tensor slabs, int64_t S, int64_t mrows, torch::Tensor params, std::vector<int64_t> off,
             torch::Tensor labels, c10::optional<torch::Tensor> idx, int64_t B, bool train, torch::Tensor H,
-            torch::Tensor dH, torch::Tensor dlogits, torch::Tensor stats, c10::optional<torch::Tensor> w2bf) {
+            torch::Tensor dH, torch::Tensor dlogits, torch::Tensor stats, c10::optional<torch::Tensor> w2bf,
+            c10::optional<torch::Tensor> step_scal, c10::optional<torch::Tensor> adam_t, int64_t t_off, double lr,
+            double b1, double b2) {
   const c10::DeviceGuard g(params.device());
+  float* ssp = optr<float>(step_scal, torch::kFloat32, 2, "step_scal");
+  TORCH_CHECK(!ssp || adam_t.has_value(), "head: step_scal needs adam_t");
+  const int* tp = ssp ? ptr<int>(*adam_t, torch::kInt32, 1, "adam_t", 4) : nullptr;
   if (!train && mrows > 128) check_eval_batch(int(B), int(mrows));
   else check_batch(int(B), int(mrows));
   Offsets o = offsets(off);
@@ -160,18 +170,30 @@ void k_head(torch::Tensor slabs, int64_t S, int64_t mrows, torch::Tensor params,
               reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(H, torch::kBFloat16, mrows * 2048, "H")),
               reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(dH, torch::kBFloat16, mrows * 2048, "dH")),
               ptr<float>(dlogits, torch::kFloat32, mrows * 10, "dlogits"), ptr<float>(stats, torch::kFloat32, 2, "stats", 4),
-              reinterpret_cast<const uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")),
-              stream());
+              reinterpret_cast<const uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")), ssp, tp,
+              int(t_off), cfg(lr, b1, b2, 0.0, 0.0, c10::nullopt), stream());
 }
 
-AdamCfg cfg(double lr, double b1, double b2, double eps, double wd) {
-  return AdamCfg{float(lr), float(b1), float(b2), float(eps), float(wd)};
+// Adam's step scalars as the Adam roles compute them inline, one lane per step: steps
+// adam_t[0] + t_off + i for the out.numel() / 2 pairs of out
+void k_adam_scal_probe(torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2, torch::Tensor out) {
+  const c10::DeviceGuard g(out.device());
+  const int64_t n = out.numel() / 2;
+  TORCH_CHECK(n >= 1 && out.numel() == 2 * n && n <= (1 << 20), "adam_scal_probe: out holds pairs");
+  p2cnn::adam_scal_probe(ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off),
+                         cfg(lr, b1, b2, 0.0, 0.0, c10::nullopt), ptr<float>(out, torch::kFloat32, 2 * n, "out", 8),
+                         int(n), stream());
+}
+
+AdamCfg cfg(double lr, double b1, double b2, double eps, double wd, const c10::optional<torch::Tensor>& scal) {
+  return AdamCfg{float(lr), float(b1), float(b2), float(eps), float(wd),
+                 optr<float>(scal, torch::kFloat32, 2, "scal")};
 }
 
 void k_fc1_wgrad_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::Tensor params, torch::Tensor m,
                       torch::Tensor v, c10::optional<torch::Tensor> gdump, torch::Tensor w1bf, c10::optional<torch::Tensor> w1tbf,
                       std::vector<int64_t> off, torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2,
-                      double eps, double wd) {
+                      double eps, double wd, c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(params.device());
   TORCH_CHECK(mrows == 32 || mrows == 64, "mrows must be 32 or 64");
   Offsets o = offsets(off);
@@ -183,14 +205,16 @@ void k_fc1_wgrad_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::
                         optr<float>(gdump, torch::kFloat32, n, "gdump"),
                         reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1bf, torch::kBFloat16, 2048 * 3136, "w1bf")),
                         reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf")),
-                        o, ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd), stream());
+                        o, ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd, scal),
+                        stream());
 }
 
 void k_route_fc2(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, int64_t mrows, int64_t B,
                  torch::Tensor dc2m, torch::Tensor gb, torch::Tensor dlogits, torch::Tensor H, torch::Tensor params,
                  torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> gdump, std::vector<int64_t> off,
                  torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2, double eps, double wd,
-                 bool with_fc2, bool row_major, c10::optional<torch::Tensor> ws, c10::optional<torch::Tensor> ctr) {
+                 bool with_fc2, bool row_major, c10::optional<torch::Tensor> ws, c10::optional<torch::Tensor> ctr,
+                 c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(dH.device());
   check_batch(int(B), int(mrows));
   TORCH_CHECK(mrows <= 64, "route_fc2: mrows must be 32 or 64");
@@ -215,11 +239,11 @@ void k_route_fc2(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, int64_t 
     float* wsp = optr<float>(ws, torch::kFloat32, 98 * 2 * mrows * 32, "ws");
     int* cp = optr<int>(ctr, torch::kInt32, 98, "ctr", 4);
     p2cnn::route_fc2_rm(dHp, w1p, am2p, int(mrows), int(B), dc2p, gbp, dlp, Hp, pp, mp, vp, gd, o, tp, int(t_off),
-                        cfg(lr, b1, b2, eps, wd), with_fc2, wsp, cp, stream());
+                        cfg(lr, b1, b2, eps, wd, scal), with_fc2, wsp, cp, stream());
   } else {
     // w1 is the W1^T shadow [3136][2048]
     p2cnn::route_fc2(dHp, w1p, am2p, int(mrows), int(B), dc2p, gbp, dlp, Hp, pp, mp, vp, gd, o, tp, int(t_off),
-                     cfg(lr, b1, b2, eps, wd), with_fc2, stream());
+                     cfg(lr, b1, b2, eps, wd, scal), with_fc2, stream());
   }
 }
 
@@ -254,7 +278,8 @@ int64_t k_route_rm_fc1(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, in
                        torch::Tensor dc2m, torch::Tensor gb, torch::Tensor dlogits, torch::Tensor H, torch::Tensor params,
                        torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> gdump, std::vector<int64_t> off,
                        torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2, double eps, double wd,
-                       bool with_fc2, torch::Tensor a1, torch::Tensor w1_write, int64_t n_tiles) {
+                       bool with_fc2, torch::Tensor a1, torch::Tensor w1_write, int64_t n_tiles,
+                       c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(dH.device());
   check_batch(int(B), int(mrows));
   TORCH_CHECK(mrows <= 64, "route_rm_fc1: mrows must be 32 or 64");
@@ -262,7 +287,7 @@ int64_t k_route_rm_fc1(torch::Tensor dH, torch::Tensor w1, torch::Tensor am2, in
               p2cnn::kFc1Tiles, "]");
   Offsets o = offsets(off);
   p2cnn::Fc1Args fc = fc1_args(dH, a1, mrows, params, m, v, gdump, w1_write, c10::nullopt, o, adam_t, t_off,
-                               cfg(lr, b1, b2, eps, wd));
+                               cfg(lr, b1, b2, eps, wd, scal));
   fc.w1bf = reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w1, torch::kBFloat16, 2048 * 3136, "w1"));
   // the hazard the second shadow buffer removes: a hosted tile rewriting W1 rows a routing block still reads
   TORCH_CHECK(n_tiles == 0 || fc.w1bf != fc.w1bf_w,
@@ -308,7 +333,7 @@ int64_t k_conv2_bwd_fc1(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1
                         torch::Tensor v, c10::optional<torch::Tensor> gdump, torch::Tensor w1bf,
                         c10::optional<torch::Tensor> w1tbf, std::vector<int64_t> off, torch::Tensor adam_t,
                         int64_t t_off, double lr, double b1, double b2, double eps, double wd, int64_t n_tiles,
-                        int64_t first_tile) {
+                        int64_t first_tile, c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(dc2m.device());
   TORCH_CHECK(mrows == 32 || mrows == 64, "conv2_bwd_fc1: mrows must be 32 or 64");
   TORCH_CHECK(n_tiles >= 0 && n_tiles <= p2cnn::kFc1Tiles, "conv2_bwd_fc1: n_tiles ", n_tiles, " outside [0, ",
@@ -317,7 +342,7 @@ int64_t k_conv2_bwd_fc1(torch::Tensor dc2m, torch::Tensor p1s, torch::Tensor am1
               " + n_tiles ", n_tiles, " outside [0, ", p2cnn::kFc1Tiles, "]");
   Offsets o = offsets(off);
   const p2cnn::Fc1Args fc =
-      fc1_args(dH, a1, mrows, params, m, v, gdump, w1bf, w1tbf, o, adam_t, t_off, cfg(lr, b1, b2, eps, wd));
+      fc1_args(dH, a1, mrows, params, m, v, gdump, w1bf, w1tbf, o, adam_t, t_off, cfg(lr, b1, b2, eps, wd, scal));
   return conv2_bwd_impl(dc2m, p1s, am1, w2q, x, idx, wslab1, wslab2, B, fc, n_tiles, first_tile);
 }
 
@@ -325,7 +350,7 @@ void k_conv_adam(torch::Tensor wslab1, torch::Tensor wslab2, torch::Tensor gb, i
                  torch::Tensor m,
                  torch::Tensor v, c10::optional<torch::Tensor> gdump, torch::Tensor w2r, torch::Tensor w2q,
                  std::vector<int64_t> off, torch::Tensor adam_t, int64_t t_off, double lr, double b1, double b2,
-                 double eps, double wd) {
+                 double eps, double wd, c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(params.device());
   Offsets o = offsets(off);
   const int64_t n = params_end(o);
@@ -337,7 +362,8 @@ void k_conv_adam(torch::Tensor wslab1, torch::Tensor wslab2, torch::Tensor gb, i
                    ptr<float>(v, torch::kFloat32, n, "v"), optr<float>(gdump, torch::kFloat32, n, "gdump"),
                    reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2r, torch::kBFloat16, 51200, "w2r")),
                    reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2q, torch::kBFloat16, 51200, "w2q")), o,
-                   ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd), stream());
+                   ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd, scal),
+                   stream());
 }
 
 void k_fc1_conv_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::Tensor wslab1, torch::Tensor wslab2,
@@ -345,7 +371,8 @@ void k_fc1_conv_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::T
                      c10::optional<torch::Tensor> gdump, torch::Tensor w1bf, c10::optional<torch::Tensor> w1tbf, torch::Tensor w2r,
                      torch::Tensor w2q, std::vector<int64_t> off, torch::Tensor adam_t, int64_t t_off, double lr,
                      double b1, double b2, double eps, double wd, c10::optional<torch::Tensor> dlogits,
-                     c10::optional<torch::Tensor> H, c10::optional<torch::Tensor> w2bf, int64_t first_tile) {
+                     c10::optional<torch::Tensor> H, c10::optional<torch::Tensor> w2bf, int64_t first_tile,
+                     c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(params.device());
   check_batch(int(B), int(mrows));
   TORCH_CHECK(mrows <= 64, "fc1_conv_adam: mrows must be 32 or 64");
@@ -366,7 +393,7 @@ void k_fc1_conv_adam(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torch::T
       reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf")),
       reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2r, torch::kBFloat16, 51200, "w2r")),
       reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2q, torch::kBFloat16, 51200, "w2q")), o,
-      ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd),
+      ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd, scal),
       optr<float>(dlogits, torch::kFloat32, B * 10, "dlogits"),
       reinterpret_cast<const uint16_t*>(optr<at::BFloat16>(H, torch::kBFloat16, B * 2048, "H")),
       reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")), int(first_tile),
@@ -384,7 +411,7 @@ void k_fc1_conv_adam_fwd(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torc
                          c10::optional<torch::Tensor> dlogits, c10::optional<torch::Tensor> H,
                          c10::optional<torch::Tensor> w2bf, torch::Tensor x, c10::optional<torch::Tensor> idx,
                          torch::Tensor p1, torch::Tensor am1, torch::Tensor p1s, torch::Tensor a1n, torch::Tensor am2,
-                         int64_t Bn, torch::Tensor sync) {
+                         int64_t Bn, torch::Tensor sync, c10::optional<torch::Tensor> scal) {
   const c10::DeviceGuard g(params.device());
   check_batch(int(B), int(mrows));
   check_batch(int(Bn), int(mrows));
@@ -417,7 +444,7 @@ void k_fc1_conv_adam_fwd(torch::Tensor dH, torch::Tensor a1, int64_t mrows, torc
       reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w1tbf, torch::kBFloat16, 2048 * 3136, "w1tbf")),
       reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2r, torch::kBFloat16, 51200, "w2r")),
       reinterpret_cast<uint16_t*>(ptr<at::BFloat16>(w2q, torch::kBFloat16, 51200, "w2q")), o,
-      ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd),
+      ptr<int>(adam_t, torch::kInt32, 1, "adam_t", 4), int(t_off), cfg(lr, b1, b2, eps, wd, scal),
       optr<float>(dlogits, torch::kFloat32, B * 10, "dlogits"),
       reinterpret_cast<const uint16_t*>(optr<at::BFloat16>(H, torch::kBFloat16, B * 2048, "H")),
       reinterpret_cast<uint16_t*>(optr<at::BFloat16>(w2bf, torch::kBFloat16, 10 * 2048, "w2bf")), f, stream());
@@ -458,31 +485,51 @@ void register_cnn(pybind11::module& m) {
   c.def("head", &k_head, pybind11::arg("slabs"), pybind11::arg("S"), pybind11::arg("mrows"), pybind11::arg("params"),
         pybind11::arg("off"), pybind11::arg("labels"), pybind11::arg("idx"), pybind11::arg("B"), pybind11::arg("train"),
         pybind11::arg("H"), pybind11::arg("dH"), pybind11::arg("dlogits"), pybind11::arg("stats"),
-        pybind11::arg("w2bf") = pybind11::none());
+        pybind11::arg("w2bf") = pybind11::none(), pybind11::arg("step_scal") = pybind11::none(),
+        pybind11::arg("adam_t") = pybind11::none(), pybind11::arg("t_off") = 0, pybind11::arg("lr") = 0.0,
+        pybind11::arg("b1") = 0.0, pybind11::arg("b2") = 0.0);
+  c.def("adam_scal_probe", &k_adam_scal_probe, "Adam's step scalars of steps adam_t[0] + t_off + i as an Adam role computes them inline -> out[2 i], out[2 i + 1]");
   c.def("route_fc2", &k_route_fc2, pybind11::arg("dH"), pybind11::arg("w1"), pybind11::arg("am2"), pybind11::arg("mrows"), pybind11::arg("B"),
         pybind11::arg("dc2m"), pybind11::arg("gb"), pybind11::arg("dlogits"), pybind11::arg("H"), pybind11::arg("params"), pybind11::arg("m"), pybind11::arg("v"),
         pybind11::arg("gdump"), pybind11::arg("off"), pybind11::arg("adam_t"), pybind11::arg("t_off"), pybind11::arg("lr"), pybind11::arg("b1"),
         pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd"), pybind11::arg("with_fc2") = true, pybind11::arg("row_major") = false,
-        pybind11::arg("ws") = pybind11::none(), pybind11::arg("ctr") = pybind11::none());
-  c.def("fc1_wgrad_adam", &k_fc1_wgrad_adam);
-  c.def("conv2_bwd", &k_conv2_bwd);
+        pybind11::arg("ws") = pybind11::none(), pybind11::arg("ctr") = pybind11::none(),
+        pybind11::arg("scal") = pybind11::none());
   namespace py = pybind11;
-  c.def("route_rm_fc1", &k_route_rm_fc1,
+  c.def("fc1_wgrad_adam", &k_fc1_wgrad_adam, py::arg("dH"), py::arg("a1"), py::arg("mrows"), py::arg("params"),
+        py::arg("m"), py::arg("v"), py::arg("gdump"), py::arg("w1bf"), py::arg("w1tbf"), py::arg("off"),
+        py::arg("adam_t"), py::arg("t_off"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
+        py::arg("scal") = py::none());
+  c.def("conv2_bwd", &k_conv2_bwd);
+  c.def("route_rm_fc1", &k_route_rm_fc1, py::arg("dH"), py::arg("w1"), py::arg("am2"), py::arg("mrows"), py::arg("B"),
+        py::arg("dc2m"), py::arg("gb"), py::arg("dlogits"), py::arg("H"), py::arg("params"), py::arg("m"), py::arg("v"),
+        py::arg("gdump"), py::arg("off"), py::arg("adam_t"), py::arg("t_off"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("with_fc2"), py::arg("a1"), py::arg("w1_write"),
+        py::arg("n_tiles"), py::arg("scal") = py::none(),
         "the row-major dA1 routing launch hosting FC1 tiles [0, n_tiles), which write w1_write; returns the tiles hosted");
   c.def("conv2_bwd_fc1", &k_conv2_bwd_fc1, py::arg("dc2m"), py::arg("p1s"), py::arg("am1"), py::arg("w2q"), py::arg("x"),
         py::arg("idx"), py::arg("wslab1"), py::arg("wslab2"), py::arg("B"), py::arg("dH"), py::arg("a1"), py::arg("mrows"),
         py::arg("params"), py::arg("m"), py::arg("v"), py::arg("gdump"), py::arg("w1bf"), py::arg("w1tbf"), py::arg("off"),
         py::arg("adam_t"), py::arg("t_off"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
-        py::arg("n_tiles"), py::arg("first_tile") = 0,
+        py::arg("n_tiles"), py::arg("first_tile") = 0, py::arg("scal") = py::none(),
         "conv2_bwd hosting n_tiles FC1 weight-gradient + Adam tiles from first_tile on; returns the tiles hosted");
-  c.def("conv_adam", &k_conv_adam);
+  c.def("conv_adam", &k_conv_adam, py::arg("wslab1"), py::arg("wslab2"), py::arg("gb"), py::arg("B"), py::arg("params"),
+        py::arg("m"), py::arg("v"), py::arg("gdump"), py::arg("w2r"), py::arg("w2q"), py::arg("off"), py::arg("adam_t"),
+        py::arg("t_off"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
+        py::arg("scal") = py::none());
   c.def("fc1_conv_adam", &k_fc1_conv_adam, pybind11::arg("dH"), pybind11::arg("a1"), pybind11::arg("mrows"), pybind11::arg("wslab1"),
         pybind11::arg("wslab2"), pybind11::arg("gb"), pybind11::arg("B"), pybind11::arg("params"), pybind11::arg("m"), pybind11::arg("v"), pybind11::arg("gdump"),
         pybind11::arg("w1bf"), pybind11::arg("w1tbf"), pybind11::arg("w2r"), pybind11::arg("w2q"), pybind11::arg("off"), pybind11::arg("adam_t"),
         pybind11::arg("t_off"), pybind11::arg("lr"), pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd"),
         pybind11::arg("dlogits") = pybind11::none(), pybind11::arg("H") = pybind11::none(),
-        pybind11::arg("w2bf") = pybind11::none(), pybind11::arg("first_tile") = 0);
-  c.def("fc1_conv_adam_fwd", &k_fc1_conv_adam_fwd);
+        pybind11::arg("w2bf") = pybind11::none(), pybind11::arg("first_tile") = 0,
+        pybind11::arg("scal") = pybind11::none());
+  c.def("fc1_conv_adam_fwd", &k_fc1_conv_adam_fwd, py::arg("dH"), py::arg("a1"), py::arg("mrows"), py::arg("wslab1"),
+        py::arg("wslab2"), py::arg("gb"), py::arg("B"), py::arg("params"), py::arg("m"), py::arg("v"), py::arg("gdump"),
+        py::arg("w1bf"), py::arg("w1tbf"), py::arg("w2r"), py::arg("w2q"), py::arg("off"), py::arg("adam_t"),
+        py::arg("t_off"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("dlogits"),
+        py::arg("H"), py::arg("w2bf"), py::arg("x"), py::arg("idx"), py::arg("p1"), py::arg("am1"), py::arg("p1s"),
+        py::arg("a1n"), py::arg("am2"), py::arg("Bn"), py::arg("sync"), py::arg("scal") = py::none());
   c.def("pack_shadows", &k_pack_shadows, pybind11::arg("params"), pybind11::arg("off"), pybind11::arg("w2r"),
         pybind11::arg("w2q"), pybind11::arg("w1bf"), pybind11::arg("w1tbf"), pybind11::arg("w2bf") = pybind11::none());
   c.def("wgrad_groups", [](int64_t B) { return int64_t(p2cnn::wgrad_groups(int(B))); },

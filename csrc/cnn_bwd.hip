@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "cnn.h"
+#include "cnn_adam_dev.h"
 #include "cnn_fwd_dev.h"
 #include "common.h"
 
@@ -35,16 +36,6 @@ P2_DEVICE uint4 pack8(const uint16_t (&v)[8]) {
   return q;
 }
 
-struct AdamScal {
-  float step_size, inv_sqrt_bc2;
-};
-P2_DEVICE AdamScal adam_scal(const AdamCfg& c, const int* t, int t_off) {
-  const float tt = float(*t + t_off);
-  AdamScal s;
-  s.step_size = c.lr / (1.f - powf(c.beta1, tt));
-  s.inv_sqrt_bc2 = 1.f / sqrtf(1.f - powf(c.beta2, tt));
-  return s;
-}
 // m / (sqrt(v) c + eps) with the hardware square root and reciprocal (v_sqrt_f32,
 // v_rcp_f32: 1 ulp each) instead of the correctly rounded sequences (~20 VALU
 // instructions per element more: the Adam streams are issue-bound beside their
@@ -75,6 +66,21 @@ P2_DEVICE float adam_apply(float* __restrict__ p, float* __restrict__ m, float* 
   return pv;
 }
 
+// adam_scal as an Adam role of this file computes it inline (cfg.scal null), one lane per
+// step: lane i writes the scalars of step (*adam_t + t_off + i) to out[2 i], out[2 i + 1]
+__global__ void adam_scal_probe_kernel(const int* __restrict__ adam_t, int t_off, AdamCfg cfg, float* __restrict__ out,
+                                       int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cfg.scal = nullptr;
+  const AdamScal s = adam_scal(cfg, adam_t, t_off + i);
+  out[2 * i] = s.step_size;
+  out[2 * i + 1] = s.inv_sqrt_bc2;
+}
+void adam_scal_probe(const int* adam_t, int t_off, AdamCfg cfg, float* out, int n, hipStream_t s) {
+  hipLaunchKernelGGL(adam_scal_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, s, adam_t, t_off, cfg, out, n);
+}
+
 // ---------------------------------------------------------------------------
 // 5+6. One launch, two independent block roles (both only need the head's
 //    outputs, so sharing a launch saves a kernel boundary):
@@ -103,6 +109,7 @@ P2_DEVICE void fc2_role(int blk, const float* __restrict__ dlogits, const uint16
   if (e >= nW + kCls) return;
   const int64_t pi = e < nW ? off.l2w + e : off.l2b + (e - nW);
   float pv = p[pi], mv = m[pi], vv = v[pi];  // issued before the reduction's loads
+  const AdamScal s = adam_scal(cfg, adam_t, t_off);  // before the role's first store: a scalar load
   float g = 0.f;
   if (e < nW) {
     const int c = e / kHid, k = e % kHid;
@@ -119,7 +126,6 @@ P2_DEVICE void fc2_role(int blk, const float* __restrict__ dlogits, const uint16
     for (int b = 0; b < B; ++b) g += dlogits[b * kCls + c];
   }
   if (gdump) gdump[pi] = g;
-  const AdamScal s = adam_scal(cfg, adam_t, t_off);
   adam_regs(pv, mv, vv, g, cfg, s);
   p[pi] = pv;
   m[pi] = mv;

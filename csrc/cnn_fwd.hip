@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "cnn.h"
+#include "cnn_adam_dev.h"
 #include "cnn_fwd_dev.h"
 #include "common.h"
 
@@ -578,9 +579,23 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ sla
                                                    const int64_t* __restrict__ idx, int B, int train,
                                                    uint16_t* __restrict__ H, uint16_t* __restrict__ dH,
                                                    float* __restrict__ dlogits,
-                                                   float* __restrict__ stats, const uint16_t* __restrict__ w2bf) {
+                                                   float* __restrict__ stats, const uint16_t* __restrict__ w2bf,
+                                                   float* __restrict__ step_scal, const int* __restrict__ adam_t,
+                                                   int t_off, AdamCfg cfg) {
   __shared__ float red[4][kCls];
   __shared__ float dl[kCls];
+  // Workgroup mrows exists only in a training launch with step_scal (head()): one lane
+  // computes Adam's scalars of this step, once for all its Adam roles (AdamCfg::scal), on
+  // a CU the sample workgroups leave idle.  (On a lane of workgroup 0, behind its first
+  // barrier, the ~370 dependent VALU instructions outlasted thread 0's softmax: the
+  // launch grew by 0.4 us, profiles/cnn_step_scalars.md.)
+  if (int(blockIdx.x) == mrows) {
+    if (train && step_scal && threadIdx.x == 0) {
+      const AdamScal sc = adam_scal_compute(cfg, adam_t, t_off);
+      *reinterpret_cast<float2*>(step_scal) = make_float2(sc.step_size, sc.inv_sqrt_bc2);
+    }
+    return;
+  }
   const int b = blockIdx.x, tid = threadIdx.x, k0 = tid * 8;
   const int wave = tid >> 6, lane = tid & 63;
   if (b >= B) {
@@ -701,9 +716,13 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ sla
 
 void head(const float* slabs, int S, int mrows, const float* params, Offsets off, const int64_t* labels,
           const int64_t* idx, int B, int train, uint16_t* H, uint16_t* dH, float* dlogits,
-          float* stats, const uint16_t* w2bf, hipStream_t s) {
-  hipLaunchKernelGGL(head_kernel, dim3(train ? mrows : B), dim3(256), 0, s, slabs, S, mrows, params + off.l1b,
-                     params + off.l2w, params + off.l2b, labels, idx, B, train, H, dH, dlogits, stats, w2bf);
+          float* stats, const uint16_t* w2bf, float* step_scal, const int* adam_t, int t_off, AdamCfg cfg,
+          hipStream_t s) {
+  if (!train) step_scal = nullptr;
+  // one workgroup per sample row (evaluation: per sample), plus the step-scalar workgroup
+  hipLaunchKernelGGL(head_kernel, dim3((train ? mrows : B) + (step_scal ? 1 : 0)), dim3(256), 0, s, slabs, S, mrows,
+                     params + off.l1b, params + off.l2w, params + off.l2b, labels, idx, B, train, H, dH, dlogits,
+                     stats, w2bf, step_scal, adam_t, t_off, cfg);
 }
 
 // ---------------------------------------------------------------------------

@@ -93,6 +93,12 @@ FC1_TILES = 1600
 # next fc1_slice tiles.  288 tiles are 144 two-tile workgroups: with the 112 routing
 # workgroups exactly one per CU.  0: no hopping, the plain routing launch.
 ROUTE_SLICE_DEFAULT = 288
+# Adam's two step scalars (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) computed once per step
+# by one lane of the head launch and read by every Adam role of the step from a 16-byte
+# device buffer, instead of two powf, a square root and two divisions in each of their
+# threads -- 371 of the 804 VALU instructions of an FC1 tile (profiles/cnn_step_scalars.md).
+# The same device function on the same inputs: bitwise-equal results.  "0": computed inline.
+_STEP_SCALARS = os.environ.get("P2PFL_CNN_STEP_SCALARS", "1") != "0"
 _NAMES = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "l1.weight", "l1.bias", "l2.weight", "l2.bias")
 FEAT, HID = 3136, 2048
 
@@ -113,6 +119,7 @@ class FusedCNNEngine:
         split_fc1: Optional[int] = None,
         fc1_slice: Optional[int] = None,
         route_slice: Optional[int] = None,
+        step_scalars: Optional[bool] = None,
     ) -> None:
         self.C = ops.ext().cnn
         self.C.init()
@@ -189,6 +196,8 @@ class FusedCNNEngine:
         self.dc2m, self.gb = z(M * 64 * 224, dt=bf), z(M * FEAT)
         self.wslab1, self.wslab2 = z(M * 7 * 832), z(self.C.wgrad_groups(M) * 51200)
         self.stats = z(2)
+        # Adam's step scalars, written by every training head launch (None: the inline arm)
+        self.step_scal = z(4) if (_STEP_SCALARS if step_scalars is None else step_scalars) else None
         # split-K partials + tickets of the routing kernel (tickets return to zero after every launch)
         split = self.route_rm and _ROUTE_SPLIT
         self.route_ws = z(98 * 2 * M * 32) if split else None
@@ -240,9 +249,11 @@ class FusedCNNEngine:
         return (self.lr, self.betas[0], self.betas[1], self.eps, self.wd)
 
     def forward(self, x: torch.Tensor, labels: torch.Tensor, idx: Optional[torch.Tensor], B: int, stats: torch.Tensor, train: bool,
-                convs: bool = True) -> None:
+                convs: bool = True, t_off: Optional[int] = None) -> None:
         """The forward pass (``convs`` False: conv1 / conv2 already ran -- inside the
-        previous step's last launch -- only the FC1 GEMM and the head remain)."""
+        previous step's last launch -- only the FC1 GEMM and the head remain).  With
+        ``t_off`` (a training step) the head also leaves Adam's scalars of step
+        ``adam_t[0] + t_off`` in ``step_scal`` for the step's Adam launches."""
         C, M = self.C, self.mrows
         if not convs:
             pass
@@ -253,6 +264,10 @@ class FusedCNNEngine:
             C.conv1_fwd(x, idx, self.params, self.off, self.p1, self.am1, self.p1s if train else None, B)
             C.conv2_fwd(self.p1, self.w2r, self.params, self.off, self.a1, self.am2, B, M)
         C.gemm_skinny(self.a1, self.w1_cur, self.slabs1, M, HID, FEAT, self.S1)
+        if train and t_off is not None and self.step_scal is not None:
+            C.head(self.slabs1, self.S1, M, self.params, self.off, labels, idx, B, train, self.H, self.dH, self.dlogits,
+                   stats, self.w2bf, self.step_scal, self.adam_t, t_off, self.lr, *self.betas)
+            return
         C.head(self.slabs1, self.S1, M, self.params, self.off, labels, idx, B, train, self.H, self.dH, self.dlogits, stats,
                self.w2bf)
 
@@ -304,26 +319,33 @@ class FusedCNNEngine:
         ``fc1_slice`` = 448 in conv2_bwd: routing 8.0 -> 9.2 us, the Adam launch
         23.3 -> 17.6 us, the captured step 72.0 -> 68.4 us (profiles/cnn_route_slice.md);
         bitwise-equal results.  In-place steps host nothing in the routing launch.
+        Adam's two step scalars are computed once per step, by one lane of an extra
+        workgroup of the head launch, into ``step_scal``; every Adam role of the step
+        (FC1 tiles in all three launches, FC2, conv parameters, FC1 bias) reads them
+        instead of two ``powf``, a square root and two divisions per thread -- 371 of
+        an FC1 tile's 804 VALU instructions.  conv2_bwd_fc1 16.9 -> 15.8 us, the Adam
+        launch 17.6 -> 17.1 us, the captured step 68.3 -> 66.6 us with the slices
+        unchanged (profiles/cnn_step_scalars.md); bitwise-equal results.
         """
         if B > self.mrows:
             raise ValueError(f"batch {B} > engine capacity {self.mrows}")
         if hop and not (self._hop_arm and nxt is None and not fwd_done):
             raise ValueError("only the default step can hop between the W1 shadow buffers")
-        C, M, a = self.C, self.mrows, self._adam()
-        self.forward(x, labels, idx, B, stats, True, convs=not fwd_done)
+        C, M, a, sc = self.C, self.mrows, self._adam(), self.step_scal
+        self.forward(x, labels, idx, B, stats, True, convs=not fwd_done, t_off=t_off)
         if hop:
             # the forward and the routing read the current W1 shadow, every FC1 tile of the
             # step writes the other buffer: the routing launch can host tiles [0, route_slice)
             w1r, w1w = self.w1_cur, self._w1s[1 - self._wp]
             nr = C.route_rm_fc1(self.dH, w1r, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H, self.params,
                                 self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, False, self.a1, w1w,
-                                self.route_slice)
+                                self.route_slice, sc)
             na = nr + C.conv2_bwd_fc1(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B,
                                       self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, w1w, None,
-                                      self.off, self.adam_t, t_off, *a, self.fc1_slice, nr)
+                                      self.off, self.adam_t, t_off, *a, self.fc1_slice, nr, sc)
             C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
                             self.gdump, w1w, None, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
-                            self.dlogits, self.H, self.w2bf, na)
+                            self.dlogits, self.H, self.w2bf, na, sc)
             self._wp ^= 1
             return
         if _MERGED_ADAM:
@@ -332,16 +354,16 @@ class FusedCNNEngine:
             # Adam stream (HBM-bound)
             C.route_fc2(self.dH, self.w1_route, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H,
                         self.params, self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, False, self.route_rm,
-                        self.route_ws, self.route_ctr)
+                        self.route_ws, self.route_ctr, sc)
             if nxt is None and not fwd_done and self.fc1_slice:
                 # the conv backward hosts the first FC1 tiles; the Adam launch takes the rest
                 # (not on the next-forward-in-Adam arm, whose steps pass nxt or fwd_done)
                 na = C.conv2_bwd_fc1(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B,
                                      self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1_cur,
-                                     self.w1tbf, self.off, self.adam_t, t_off, *a, self.fc1_slice)
+                                     self.w1tbf, self.off, self.adam_t, t_off, *a, self.fc1_slice, 0, sc)
                 C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
                                 self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
-                                self.dlogits, self.H, self.w2bf, na)
+                                self.dlogits, self.H, self.w2bf, na, sc)
                 return
             C.conv2_bwd(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B)
             if nxt is not None and M <= 64:
@@ -351,19 +373,19 @@ class FusedCNNEngine:
                 C.fc1_conv_adam_fwd(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m,
                                     self.v, self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t,
                                     t_off, *a, self.dlogits, self.H, self.w2bf, x, idx_n, self.p1, self.am1, self.p1s,
-                                    self._a1s[1 - self._par], self.am2, Bn, self._fwd_sync)
+                                    self._a1s[1 - self._par], self.am2, Bn, self._fwd_sync, sc)
                 self._par ^= 1
                 return
             C.fc1_conv_adam(self.dH, self.a1, M, self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v,
                             self.gdump, self.w1_cur, self.w1tbf, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a,
-                            self.dlogits, self.H, self.w2bf)
+                            self.dlogits, self.H, self.w2bf, 0, sc)
             return
         C.route_fc2(self.dH, self.w1_route, self.am2, M, B, self.dc2m, self.gb, self.dlogits, self.H,
                     self.params, self.m, self.v, self.gdump, self.off, self.adam_t, t_off, *a, True, self.route_rm,
-                    self.route_ws, self.route_ctr)
-        C.fc1_wgrad_adam(self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1_cur, self.w1tbf, self.off, self.adam_t, t_off, *a)
+                    self.route_ws, self.route_ctr, sc)
+        C.fc1_wgrad_adam(self.dH, self.a1, M, self.params, self.m, self.v, self.gdump, self.w1_cur, self.w1tbf, self.off, self.adam_t, t_off, *a, sc)
         C.conv2_bwd(self.dc2m, self.p1s, self.am1, self.w2q, x, idx, self.wslab1, self.wslab2, B)
-        C.conv_adam(self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v, self.gdump, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a)
+        C.conv_adam(self.wslab1, self.wslab2, self.gb, B, self.params, self.m, self.v, self.gdump, self.w2r, self.w2q, self.off, self.adam_t, t_off, *a, sc)
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor) -> float:
         """Convenience: one eager step on a uint8 batch ``x`` [B,1,28,28] with labels ``y``; returns the loss."""

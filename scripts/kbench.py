@@ -56,6 +56,9 @@ def main() -> None:
         eng.train_step_async(x, y, None, B, stats, 1)
     torch.cuda.synchronize()
     a = eng._adam()
+    # Adam's step scalars as the warm-up steps' head launches left them (None on the inline
+    # arm, P2PFL_CNN_STEP_SCALARS=0): the Adam-carrying launches below read them like a step does
+    sc = eng.step_scal
     # Adam kernels write into the params: run them on scratch copies so repeated
     # launches do not drift the weights into NaN territory
     P, Mm, V = eng.params.clone(), eng.m.clone(), eng.v.clone()
@@ -68,7 +71,7 @@ def main() -> None:
         "conv2_fwd": lambda: C.conv2_fwd(eng.p1, eng.w2r, eng.params, eng.off, eng.a1, eng.am2, B, M),
         "conv12_fwd": lambda: C.conv12_fwd(x, None, eng.params, eng.off, eng.w2r, None, eng.am1, eng.p1s, eng.a1, eng.am2, B, M),
         "gemm_fc1": lambda: C.gemm_skinny(eng.a1, eng.w1bf, eng.slabs1, M, 2048, 3136, eng.S1),
-        "head": lambda: C.head(eng.slabs1, eng.S1, M, eng.params, eng.off, y, None, B, True, eng.H, eng.dH, eng.dlogits, stats, eng.w2bf),
+        "head": lambda: C.head(eng.slabs1, eng.S1, M, eng.params, eng.off, y, None, B, True, eng.H, eng.dH, eng.dlogits, stats, eng.w2bf, sc, eng.adam_t, 1, eng.lr, *eng.betas),
         "head_w2fp32": lambda: C.head(eng.slabs1, eng.S1, M, eng.params, eng.off, y, None, B, True, eng.H, eng.dH, eng.dlogits, stats),
         "route_fc2": lambda: C.route_fc2(eng.dH, eng.w1_route, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, True, eng.route_rm),
         "route_dA1_only": lambda: C.route_fc2(eng.dH, eng.w1bf, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, False, True),
@@ -76,10 +79,10 @@ def main() -> None:
         "route_dA1_w1t": lambda: C.route_fc2(eng.dH, w1t, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, False, False),
         "fc1_conv_adam_w1t": lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, w1t, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H),
         "fc1_conv_adam": lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a),
-        "fc2_fc1_conv_adam": lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s),
-        "fc1_wgrad_adam": lambda: C.fc1_wgrad_adam(eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a),
+        "fc2_fc1_conv_adam": lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, 0, sc),
+        "fc1_wgrad_adam": lambda: C.fc1_wgrad_adam(eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a, sc),
         "conv2_bwd": lambda: C.conv2_bwd(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B),
-        "conv_adam": lambda: C.conv_adam(eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a),
+        "conv_adam": lambda: C.conv_adam(eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, sc),
     }
     only = [s for s in args.only.split(",") if s]
 
@@ -135,9 +138,9 @@ def main() -> None:
                 continue
             w1w = eng._w1s[1]  # the hosted tiles write the shadow buffer the routing blocks do not read
             t = {
-                "route_rm_fc1": timeit(lambda: C.route_rm_fc1(eng.dH, eng.w1bf, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, False, eng.a1, w1w, r)),
-                "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, w1w, None, eng.off, eng.adam_t, 1, *a, n, r)),
-                "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, w1w, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, r + n)),
+                "route_rm_fc1": timeit(lambda: C.route_rm_fc1(eng.dH, eng.w1bf, eng.am2, M, B, eng.dc2m, eng.gb, eng.dlogits, eng.H, P, Mm, V, None, eng.off, eng.adam_t, 1, *a, False, eng.a1, w1w, r, sc)),
+                "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, w1w, None, eng.off, eng.adam_t, 1, *a, n, r, sc)),
+                "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, w1w, None, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, r + n, sc)),
             }
             t["trio"] = round(sum(t.values()), 2)
             if not args.no_graph:
@@ -148,8 +151,8 @@ def main() -> None:
             routes[f"{r}+{n}"] = t
     for n in [] if route_slices else fc1_slices:
         r = {
-            "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a, n)),
-            "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, n)),
+            "conv2_bwd_fc1": timeit(lambda: C.conv2_bwd_fc1(eng.dc2m, eng.p1s, eng.am1, eng.w2q, x, None, eng.wslab1, eng.wslab2, B, eng.dH, eng.a1, M, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.off, eng.adam_t, 1, *a, n, 0, sc)),
+            "fc2_fc1_conv_adam": timeit(lambda: C.fc1_conv_adam(eng.dH, eng.a1, M, eng.wslab1, eng.wslab2, eng.gb, B, P, Mm, V, None, eng.w1bf, eng.w1tbf, eng.w2r, eng.w2q, eng.off, eng.adam_t, 1, *a, eng.dlogits, eng.H, w2s, n, sc)),
         }
         r["pair"] = round(r["conv2_bwd_fc1"] + r["fc2_fc1_conv_adam"], 2)
         if not args.no_graph:

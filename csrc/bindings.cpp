@@ -443,6 +443,7 @@ void destroy_stream(int64_t s) { (void)hipStreamDestroy(reinterpret_cast<hipStre
 void register_cnn(pybind11::module& m);
 void register_fused(pybind11::module& m);
 void register_bn(pybind11::module& m);
+void register_gn(pybind11::module& m);
 void register_rccl(pybind11::module& m);
 void register_gemm(pybind11::module& m);
 void register_conv(pybind11::module& m);
@@ -500,6 +501,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_cnn(m);
   register_fused(m);
   register_bn(m);
+  register_gn(m);
   register_rccl(m);
   register_gemm(m);
   register_conv(m);

@@ -31,7 +31,12 @@ launch also computes the batch statistics of the BatchNorm that follows it
 the backward statistics of the one before it (:func:`~p2pfl_amd.ops.conv.bn_act_conv_bn_stats`):
 conv1 -> [bn1 apply, conv2] -> bn2 apply per BasicBlock -- fewer launches, but measured
 slower on these shapes (``profiles/r4_bn_epilogue.md``).  Evaluation (running statistics) runs the one-pass
-BN kernel of ``csrc/batchnorm.hip`` (:func:`~p2pfl_amd.ops.batchnorm.batch_norm_act`).  Optimiser: SGD with momentum 0.9 and weight decay 5e-4 (fused
+BN kernel of ``csrc/batchnorm.hip`` (:func:`~p2pfl_amd.ops.batchnorm.batch_norm_act`).
+
+``norm="group"`` builds ``GroupNorm(C // gn_channels_per_group, C)`` wherever a BatchNorm stands
+(same attribute names, no buffers): training and evaluation run the LDS-resident kernels of
+``csrc/groupnorm.hip`` (:func:`~p2pfl_amd.ops.groupnorm.group_norm_act`), one launch per
+normalisation and direction.  Optimiser: SGD with momentum 0.9 and weight decay 5e-4 (fused
 into one arena kernel by the learner), a standard federated CIFAR setup.
 """
 
@@ -45,6 +50,7 @@ from torch import nn
 
 from p2pfl_amd.models.base import FLModule, seed_everything
 from p2pfl_amd.ops.batchnorm import batch_norm_act, batch_norm_apply
+from p2pfl_amd.ops.groupnorm import group_norm_act
 from p2pfl_amd.ops.head import head_ok, head_xent
 from p2pfl_amd.ops.conv import bn_act_conv_bn_stats, conv2d, conv_bn_act, conv_bn_stats, stem_conv2d, stem_ok
 
@@ -68,6 +74,17 @@ def _pair(x):
     return x if isinstance(x, tuple) else (x, x)
 
 
+def _stats(x: torch.Tensor, conv: nn.Conv2d, norm: nn.Module):
+    """:func:`~p2pfl_amd.ops.conv.conv_bn_stats` for a BatchNorm; None for a GroupNorm, whose
+    statistics are per sample and are not computed by a convolution's launch."""
+    return None if isinstance(norm, nn.GroupNorm) else conv_bn_stats(x, conv, norm)
+
+
+def _norm_act(x: torch.Tensor, norm: nn.Module, fork: bool = False):
+    """``relu(norm(x))`` on the fused kernels of the module's kind."""
+    return (group_norm_act if isinstance(norm, nn.GroupNorm) else batch_norm_act)(x, norm, fork=fork)
+
+
 def _shortcut(sc: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """Identity, or the projection conv + BN (no activation)."""
     if isinstance(sc, nn.Identity):
@@ -78,21 +95,21 @@ def _shortcut(sc: nn.Module, x: torch.Tensor) -> torch.Tensor:
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin: int, cout: int, stride: int = 1) -> None:
+    def __init__(self, cin: int, cout: int, stride: int = 1, norm=nn.BatchNorm2d) -> None:
         super().__init__()
         self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(cout)
+        self.bn1 = norm(cout)
         self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(cout)
+        self.bn2 = norm(cout)
         self.shortcut: nn.Module = nn.Identity()
         if stride != 1 or cin != cout:
-            self.shortcut = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+            self.shortcut = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), norm(cout))
 
     def forward(self, x):
         """``x``: a tensor or the (conv input, shortcut input) pair of a forked BN output;
         returns such a pair (see ``_FORK``)."""
         x, xs = _pair(x)
-        st = conv_bn_stats(x, self.conv1, self.bn1)
+        st = _stats(x, self.conv1, self.bn1)
         st = bn_act_conv_bn_stats(st, self.bn1, True, self.conv2, self.bn2) if st is not None else None
         if st is not None:  # conv1 -> [bn1 apply, conv2] -> bn2 apply: 3 launches forward
             return batch_norm_apply(st[0], self.bn2, st[1], st[2], st[3], _shortcut(self.shortcut, xs), True, _FORK)
@@ -103,23 +120,23 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, cin: int, width: int, stride: int = 1) -> None:
+    def __init__(self, cin: int, width: int, stride: int = 1, norm=nn.BatchNorm2d) -> None:
         super().__init__()
         cout = width * self.expansion
         self.conv1 = nn.Conv2d(cin, width, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(width)
+        self.bn1 = norm(width)
         self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(width)
+        self.bn2 = norm(width)
         self.conv3 = nn.Conv2d(width, cout, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(cout)
+        self.bn3 = norm(cout)
         self.shortcut: nn.Module = nn.Identity()
         if stride != 1 or cin != cout:
-            self.shortcut = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+            self.shortcut = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), norm(cout))
 
     def forward(self, x):
         """As :meth:`BasicBlock.forward`: a tensor or a pair in, a pair out."""
         x, xs = _pair(x)
-        st = conv_bn_stats(x, self.conv1, self.bn1)
+        st = _stats(x, self.conv1, self.bn1)
         st = bn_act_conv_bn_stats(st, self.bn1, True, self.conv2, self.bn2) if st is not None else None
         st = bn_act_conv_bn_stats(st, self.bn2, True, self.conv3, self.bn3) if st is not None else None
         if st is not None:
@@ -143,17 +160,27 @@ class ResNet(FLModule):
         momentum: float = 0.9,
         weight_decay: float = 5e-4,
         seed: Optional[int] = None,
+        norm: str = "batch",
+        gn_channels_per_group: int = 16,
     ) -> None:
         super().__init__()
         if seed is not None:
             seed_everything(seed)
+        if norm == "batch":
+            make_norm = nn.BatchNorm2d
+        elif norm == "group":
+            # no buffers, no batch statistics, the same in training and evaluation (ops/groupnorm.py)
+            def make_norm(c: int) -> nn.Module:
+                return nn.GroupNorm(c // gn_channels_per_group, c)
+        else:
+            raise ValueError(f"unknown norm {norm!r}")
         self.lr_rate, self.momentum, self.weight_decay = lr_rate, momentum, weight_decay
         if stem == "cifar":
-            self.stem = nn.Sequential(nn.Conv2d(in_channels, 64, 3, 1, 1, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True))
+            self.stem = nn.Sequential(nn.Conv2d(in_channels, 64, 3, 1, 1, bias=False), make_norm(64), nn.ReLU(inplace=True))
         elif stem == "imagenet":
             self.stem = nn.Sequential(
                 nn.Conv2d(in_channels, 64, 7, 2, 3, bias=False),
-                nn.BatchNorm2d(64),
+                make_norm(64),
                 nn.ReLU(inplace=True),
                 nn.MaxPool2d(3, 2, 1),
             )
@@ -165,7 +192,7 @@ class ResNet(FLModule):
             blocks = []
             for j in range(n):
                 stride = 2 if (i > 0 and j == 0) else 1
-                blocks.append(block(cin, width, stride))
+                blocks.append(block(cin, width, stride, make_norm))
                 cin = width * block.expansion
             stages.append(nn.Sequential(*blocks))
         self.layer1, self.layer2, self.layer3, self.layer4 = stages
@@ -173,7 +200,7 @@ class ResNet(FLModule):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
@@ -191,9 +218,9 @@ class ResNet(FLModule):
                 x = x.contiguous(memory_format=torch.channels_last)
             x = conv2d(x, stem)
         if len(self.stem) > 3:
-            x = self.stem[3](batch_norm_act(x, self.stem[1]))
+            x = self.stem[3](_norm_act(x, self.stem[1]))
         else:
-            x = batch_norm_act(x, self.stem[1], fork=_FORK)
+            x = _norm_act(x, self.stem[1], fork=_FORK)
         return _pair(self.layer4(self.layer3(self.layer2(self.layer1(x)))))[0]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

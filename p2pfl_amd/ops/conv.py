@@ -509,9 +509,15 @@ def conv_bn_act(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, residual=N
     kernels, the convolution's launch computes the batch statistics (and updates the
     running ones): only the BN apply pass remains a separate launch.  Anything else
     composes :func:`conv2d` and :func:`~p2pfl_amd.ops.batchnorm.batch_norm_act`.
-    ``fork``: return the pair of :func:`~p2pfl_amd.ops.batchnorm.batch_norm_act`."""
+    ``fork``: return the pair of :func:`~p2pfl_amd.ops.batchnorm.batch_norm_act`.
+    A ``GroupNorm`` in place of ``bn`` composes :func:`conv2d` and
+    :func:`~p2pfl_amd.ops.groupnorm.group_norm_act` (no statistics in the convolution's launch)."""
     from p2pfl_amd.ops import batchnorm as bnops
 
+    if isinstance(bn, nn.GroupNorm):
+        from p2pfl_amd.ops.groupnorm import group_norm_act
+
+        return group_norm_act(conv2d(x, conv), bn, residual=residual, relu=relu, fork=fork)
     if residual is None or residual.is_contiguous(memory_format=torch.channels_last):
         st = conv_bn_stats(x, conv, bn)
         if st is not None:

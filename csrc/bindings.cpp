@@ -448,6 +448,7 @@ void register_rccl(pybind11::module& m);
 void register_gemm(pybind11::module& m);
 void register_conv(pybind11::module& m);
 void register_head(pybind11::module& m);
+void register_mlp(pybind11::module& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "p2pfl_amd native HIP/CDNA4 kernels (gfx950)";
@@ -506,4 +507,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_gemm(m);
   register_conv(m);
   register_head(m);
+  register_mlp(m);
 }

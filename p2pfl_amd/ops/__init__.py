@@ -535,6 +535,7 @@ from p2pfl_amd.ops.fused import linear as linear_blas  # noqa: E402,F401  (hipBL
 from p2pfl_amd.ops.gemm import gemm, gemm_reference, linear, linear_gelu  # noqa: E402,F401
 from p2pfl_amd.ops.conv import conv2d  # noqa: E402,F401
 from p2pfl_amd.ops.groupnorm import group_norm_act, group_norm_act_reference  # noqa: E402,F401  (csrc/groupnorm.hip)
+from p2pfl_amd.ops.mlp import mlp_ok, mlp_xent, mlp_xent_reference  # noqa: E402,F401  (csrc/mlp.hip)
 from p2pfl_amd.ops.dp import (  # noqa: E402,F401  (csrc/dp_update.hip)
     DP_BLOCK,
     DP_NOISE_MAX,

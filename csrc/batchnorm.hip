@@ -566,21 +566,6 @@ BnPlan bn_plan(int M, int C) {
   return p;
 }
 
-// Runtime flags as template booleans: fn receives std::true_type / std::false_type values.
-template <class Fn>
-static void with_flag(bool a, Fn&& fn) {
-  a ? fn(std::true_type{}) : fn(std::false_type{});
-}
-template <class Fn>
-static void with_flags(bool a, bool b, Fn&& fn) {
-  with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { fn(A, B); }); });
-}
-// fn receives a value of the activation's element type
-template <class Fn>
-static void with_dtype(bool bf16, Fn&& fn) {
-  bf16 ? fn(uint16_t{}) : fn(float{});
-}
-
 constexpr dim3 kBlock(kThreads);
 static dim3 fin_grid(int C) { return dim3((C + kFinCols - 1) / kFinCols); }
 

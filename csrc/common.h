@@ -4,6 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stdexcept>
+#include <type_traits>
 
 #define P2_DEVICE __device__ __forceinline__
 
@@ -63,6 +64,7 @@ struct Vec8<uint16_t> {
     *reinterpret_cast<uint4*>(p) = u;
   }
   static P2_DEVICE float one(const uint16_t* p) { return bf16_to_f32(*p); }
+  static P2_DEVICE void store_one(uint16_t* p, float v) { *p = f32_to_bf16(v); }
 };
 template <>
 struct Vec8<float> {
@@ -76,6 +78,7 @@ struct Vec8<float> {
     reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
   }
   static P2_DEVICE float one(const float* p) { return *p; }
+  static P2_DEVICE void store_one(float* p, float v) { *p = v; }
 };
 
 // Grid size for a grid-stride memory-bound kernel: enough blocks to cover the
@@ -87,9 +90,25 @@ inline int stream_grid(int64_t work_items, int block) {
   return int(g);
 }
 
+// Runtime flags as template booleans: fn receives std::true_type / std::false_type values.
+template <class Fn>
+static void with_flag(bool a, Fn&& fn) {
+  a ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <class Fn>
+static void with_flags(bool a, bool b, Fn&& fn) {
+  with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { fn(A, B); }); });
+}
+// fn receives a value of the activation's element type
+template <class Fn>
+static void with_dtype(bool bf16, Fn&& fn) {
+  bf16 ? fn(uint16_t{}) : fn(float{});
+}
+
 // erf, branch-free: Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 (plus fp32
 // rounding) -- ~12 VALU instructions against ~80 for the library erff, which
-// makes GELU epilogues VALU-bound (same form as fused_ops.hip's bias+GELU).
+// makes GELU epilogues and the bias+GELU kernels VALU-bound; far below the bf16
+// output rounding and inside the fp32 tests' 1e-5.
 P2_DEVICE float erf_fast(float x) {
   const float a = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, a, 1.f));

@@ -12,17 +12,38 @@ namespace {
 
 hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-bool act_dtype(const torch::Tensor& t, const char* name) {
+// what every kernel's 16-byte vector accesses need of a tensor
+void check_vec16(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32, name, " must be bf16 or fp32");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+bool act_dtype(const torch::Tensor& t, const char* name) {
+  check_vec16(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32, name, " must be bf16 or fp32");
   return t.scalar_type() == torch::kBFloat16;
 }
+
+void check_bf16(const torch::Tensor& t, const char* name) {
+  check_vec16(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+}
+
+uint16_t* bf16_ptr(const torch::Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 
 void check_f32(const torch::Tensor& t, int64_t n, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32, name, " must be contiguous fp32 on GPU");
   TORCH_CHECK(t.numel() >= n, name, " too small");
 }
+
+// a second activation of an op (dy, residual, gsum): x's shape, dtype and device, and as accessible
+void check_like(const torch::Tensor& t, const torch::Tensor& x, const char* name) {
+  act_dtype(t, name);
+  TORCH_CHECK(t.sizes() == x.sizes() && t.scalar_type() == x.scalar_type() && t.device() == x.device(), name,
+              " must match x");
+}
+
+bool present(const c10::optional<torch::Tensor>& t) { return t.has_value() && t->defined(); }
 
 // uint8 [B, C, H, W] -> bf16 [B, (H/P)(W/P), C P P] / 255
 torch::Tensor patchify_u8(torch::Tensor x, int64_t P) {
@@ -33,15 +54,8 @@ torch::Tensor patchify_u8(torch::Tensor x, int64_t P) {
   TORCH_CHECK(P > 0 && P % 8 == 0 && H % P == 0 && W % P == 0, "patchify_u8: P % 8 == 0 and P | H, W");
   auto out = torch::empty({B, (H / P) * (W / P), C * P * P}, x.options().dtype(torch::kBFloat16));
   if (out.numel() > 0)
-    p2fused::patchify_u8(x.data_ptr<uint8_t>(), reinterpret_cast<uint16_t*>(out.data_ptr()), int(B), int(C), int(H),
-                         int(W), int(P), stream());
+    p2fused::patchify_u8(x.data_ptr<uint8_t>(), bf16_ptr(out), int(B), int(C), int(H), int(W), int(P), stream());
   return out;
-}
-
-void check_bf16(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kBFloat16 &&
-                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              name, " must be a contiguous 16-byte aligned bf16 GPU tensor");
 }
 
 // y [B, N, D], cls [D], pos [N + 1, D] (bf16) -> h [B, N + 1, D]
@@ -56,9 +70,7 @@ torch::Tensor embed_tokens_fwd(torch::Tensor y, torch::Tensor cls, torch::Tensor
   TORCH_CHECK(cls.device() == y.device() && pos.device() == y.device(), "embed_tokens: devices");
   auto h = torch::empty({B, N + 1, D}, y.options());
   if (h.numel() > 0)
-    p2fused::embed_tokens_fwd(reinterpret_cast<const uint16_t*>(y.data_ptr()), reinterpret_cast<const uint16_t*>(cls.data_ptr()),
-                              reinterpret_cast<const uint16_t*>(pos.data_ptr()), reinterpret_cast<uint16_t*>(h.data_ptr()),
-                              int(B), int(N), int(D), stream());
+    p2fused::embed_tokens_fwd(bf16_ptr(y), bf16_ptr(cls), bf16_ptr(pos), bf16_ptr(h), int(B), int(N), int(D), stream());
   return h;
 }
 
@@ -72,26 +84,28 @@ std::vector<torch::Tensor> embed_tokens_bwd(torch::Tensor dh) {
   auto dpos = torch::empty({N + 1, D}, dh.options());
   auto dcls = torch::empty({D}, dh.options());
   if (dpos.numel() > 0)
-    p2fused::embed_tokens_bwd(reinterpret_cast<const uint16_t*>(dh.data_ptr()), reinterpret_cast<uint16_t*>(dy.data_ptr()),
-                              reinterpret_cast<uint16_t*>(dpos.data_ptr()), reinterpret_cast<uint16_t*>(dcls.data_ptr()),
-                              int(B), int(N), int(D), stream());
+    p2fused::embed_tokens_bwd(bf16_ptr(dh), bf16_ptr(dy), bf16_ptr(dpos), bf16_ptr(dcls), int(B), int(N), int(D), stream());
   return {dy, dpos, dcls};
+}
+
+// ---- LayerNorm ------------------------------------------------------------------
+// x [N, C] as the kernels take it and its fp32 weight; the forward and both backward bindings
+bool ln_check(const torch::Tensor& x, const torch::Tensor& w) {
+  TORCH_CHECK(x.dim() == 2, "x must be [N, C]");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= p2fused::kMaxLnCols, "C must be a multiple of 8 and <= ", p2fused::kMaxLnCols);
+  check_f32(w, C, "weight");
+  return act_dtype(x, "x");
 }
 
 std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b, double eps,
                                   c10::optional<torch::Tensor> residual) {
   const c10::DeviceGuard g(x.device());
-  TORCH_CHECK(x.dim() == 2, "x must be [N, C]");
+  const bool bf = ln_check(x, w);
   const int64_t N = x.size(0), C = x.size(1);
-  TORCH_CHECK(C % 8 == 0 && C <= p2fused::kMaxLnCols, "C must be a multiple of 8 and <= 2048");
-  const bool bf = act_dtype(x, "x");
-  check_f32(w, C, "weight");
   check_f32(b, C, "bias");
-  const bool has_res = residual.has_value() && residual->defined();
-  if (has_res) {
-    act_dtype(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes() && residual->scalar_type() == x.scalar_type(), "residual must match x");
-  }
+  const bool has_res = present(residual);
+  if (has_res) check_like(*residual, x, "residual");
   auto y = torch::empty_like(x);
   auto sum = has_res ? torch::empty_like(x) : torch::Tensor();
   auto opt = x.options().dtype(torch::kFloat32);
@@ -104,90 +118,122 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor w, torch::Tenso
   return {y, mean, rstd};
 }
 
-std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
-                                  torch::Tensor rstd, c10::optional<torch::Tensor> gsum) {
+// reduce: (dx, dgamma, dbeta); else (dx and the [G, C] partials), their column reduction left to
+// col_reduce_multi (a training step's deferred parameter-gradient reductions, ops/fused.py
+// deferred_param_grads).  The same holds for the bias+GELU backward and the column sums below.
+std::vector<torch::Tensor> ln_bwd_any(const torch::Tensor& dy, const torch::Tensor& x, const torch::Tensor& w,
+                                      const torch::Tensor& mean, const torch::Tensor& rstd,
+                                      const c10::optional<torch::Tensor>& gsum, bool reduce) {
   const c10::DeviceGuard g(x.device());
+  const bool bf = ln_check(x, w);
   const int64_t N = x.size(0), C = x.size(1);
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(), "dy must match x");
-  const bool bf = act_dtype(x, "x");
-  act_dtype(dy, "dy");
-  check_f32(w, C, "weight");
+  TORCH_CHECK(reduce || N > 0, "ln_bwd_parts: empty input");
+  check_like(dy, x, "dy");
   check_f32(mean, N, "mean");
   check_f32(rstd, N, "rstd");
-  const bool has_gs = gsum.has_value() && gsum->defined();
-  if (has_gs) {
-    act_dtype(*gsum, "gsum");
-    TORCH_CHECK(gsum->sizes() == x.sizes() && gsum->scalar_type() == x.scalar_type(), "gsum must match x");
-  }
+  const bool has_gs = present(gsum);
+  if (has_gs) check_like(*gsum, x, "gsum");
   auto dx = torch::empty_like(x);
   auto opt = x.options().dtype(torch::kFloat32);
-  auto dw = torch::empty({C}, opt), db = torch::empty({C}, opt);  // col_reduce writes every column
+  torch::Tensor pdw, pdb, dw, db;
+  if (reduce) dw = torch::empty({C}, opt), db = torch::empty({C}, opt);  // col_reduce writes every column
   if (N > 0) {
     const int G = p2fused::layer_norm_bwd_blocks(int(N));
-    auto pdw = torch::empty({G, C}, opt), pdb = torch::empty({G, C}, opt);
+    pdw = torch::empty({G, C}, opt), pdb = torch::empty({G, C}, opt);
     p2fused::layer_norm_bwd(bf, dy.data_ptr(), x.data_ptr(), w.data_ptr<float>(), mean.data_ptr<float>(),
                             rstd.data_ptr<float>(), has_gs ? gsum->data_ptr() : nullptr, dx.data_ptr(),
-                            pdw.data_ptr<float>(), pdb.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(),
-                            int(N), int(C), stream());
+                            pdw.data_ptr<float>(), pdb.data_ptr<float>(), reduce ? dw.data_ptr<float>() : nullptr,
+                            reduce ? db.data_ptr<float>() : nullptr, int(N), int(C), stream());
   } else {
     dw.zero_();
     db.zero_();
   }
-  return {dx, dw, db};
-}
-
-// The backward passes above without their column reduction: the partials are returned
-// and reduced later, many at a time, by col_reduce_multi (a training step's deferred
-// parameter-gradient reductions, ops/fused.py deferred_param_grads).
-std::vector<torch::Tensor> ln_bwd_parts(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
-                                        torch::Tensor rstd, c10::optional<torch::Tensor> gsum) {
-  const c10::DeviceGuard g(x.device());
-  const int64_t N = x.size(0), C = x.size(1);
-  TORCH_CHECK(N > 0, "ln_bwd_parts: empty input");
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(), "dy must match x");
-  const bool bf = act_dtype(x, "x");
-  act_dtype(dy, "dy");
-  check_f32(w, C, "weight");
-  check_f32(mean, N, "mean");
-  check_f32(rstd, N, "rstd");
-  const bool has_gs = gsum.has_value() && gsum->defined();
-  if (has_gs)
-    TORCH_CHECK(gsum->sizes() == x.sizes() && gsum->scalar_type() == x.scalar_type(), "gsum must match x");
-  auto dx = torch::empty_like(x);
-  auto opt = x.options().dtype(torch::kFloat32);
-  const int G = p2fused::layer_norm_bwd_blocks(int(N));
-  auto pdw = torch::empty({G, C}, opt), pdb = torch::empty({G, C}, opt);
-  p2fused::layer_norm_bwd(bf, dy.data_ptr(), x.data_ptr(), w.data_ptr<float>(), mean.data_ptr<float>(),
-                          rstd.data_ptr<float>(), has_gs ? gsum->data_ptr() : nullptr, dx.data_ptr(),
-                          pdw.data_ptr<float>(), pdb.data_ptr<float>(), nullptr, nullptr, int(N), int(C), stream());
+  if (reduce) return {dx, dw, db};
   return {dx, pdw, pdb};
 }
 
-std::vector<torch::Tensor> bias_gelu_bwd_parts(torch::Tensor dy, torch::Tensor x, torch::Tensor b) {
-  const c10::DeviceGuard g(x.device());
-  const int64_t H = x.size(-1), N = x.numel() / H;
-  TORCH_CHECK(N > 0, "bias_gelu_bwd_parts: empty input");
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(), "dy must match x");
-  const bool bf = act_dtype(x, "x");
-  act_dtype(dy, "dy");
+std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
+                                  torch::Tensor rstd, c10::optional<torch::Tensor> gsum) {
+  return ln_bwd_any(dy, x, w, mean, rstd, gsum, true);
+}
+
+std::vector<torch::Tensor> ln_bwd_parts(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
+                                        torch::Tensor rstd, c10::optional<torch::Tensor> gsum) {
+  return ln_bwd_any(dy, x, w, mean, rstd, gsum, false);
+}
+
+// ---- bias + GELU ----------------------------------------------------------------
+// x [..., H] and its fp32 bias; the forward and both backward bindings
+bool gelu_check(const torch::Tensor& x, const torch::Tensor& b) {
+  const int64_t H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, "last dim must be a multiple of 8");
   check_f32(b, H, "bias");
+  return act_dtype(x, "x");
+}
+
+torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
+  const c10::DeviceGuard g(x.device());
+  const bool bf = gelu_check(x, b);
+  auto y = torch::empty_like(x);
+  if (x.numel() > 0)
+    p2fused::bias_gelu_fwd(bf, x.data_ptr(), b.data_ptr<float>(), y.data_ptr(), x.numel(), int(x.size(-1)), stream());
+  return y;
+}
+
+std::vector<torch::Tensor> bias_gelu_bwd_any(const torch::Tensor& dy, const torch::Tensor& x, const torch::Tensor& b,
+                                             bool reduce) {
+  const c10::DeviceGuard g(x.device());
+  const bool bf = gelu_check(x, b);
+  const int64_t H = x.size(-1), N = x.numel() / std::max<int64_t>(H, 1);
+  TORCH_CHECK(reduce || N > 0, "bias_gelu_bwd_parts: empty input");
+  check_like(dy, x, "dy");
   auto dx = torch::empty_like(x);
-  auto pdb = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, x.options().dtype(torch::kFloat32));
-  p2fused::bias_gelu_bwd(bf, dy.data_ptr(), x.data_ptr(), b.data_ptr<float>(), dx.data_ptr(), pdb.data_ptr<float>(),
-                         nullptr, int(N), int(H), stream());
+  auto opt = x.options().dtype(torch::kFloat32);
+  torch::Tensor pdb, db;
+  if (reduce) db = torch::empty({H}, opt);  // col_reduce writes every column
+  if (N > 0) {
+    pdb = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, opt);
+    p2fused::bias_gelu_bwd(bf, dy.data_ptr(), x.data_ptr(), b.data_ptr<float>(), dx.data_ptr(), pdb.data_ptr<float>(),
+                           reduce ? db.data_ptr<float>() : nullptr, int(N), int(H), stream());
+  } else {
+    db.zero_();
+  }
+  if (reduce) return {dx, db};
   return {dx, pdb};
 }
 
-torch::Tensor column_sum_parts(torch::Tensor x) {
+std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor b) {
+  return bias_gelu_bwd_any(dy, x, b, true);
+}
+
+std::vector<torch::Tensor> bias_gelu_bwd_parts(torch::Tensor dy, torch::Tensor x, torch::Tensor b) {
+  return bias_gelu_bwd_any(dy, x, b, false);
+}
+
+// ---- column sums ----------------------------------------------------------------
+// reduce: the [H] sums (fp32, or bf16 with bf16_out); else the [S, H] partials of a non-empty x
+torch::Tensor column_sum_any(const torch::Tensor& x, bool bf16_out, bool reduce) {
   const c10::DeviceGuard g(x.device());
-  TORCH_CHECK(x.dim() == 2 && x.size(0) > 0, "x must be a non-empty [N, H]");
+  TORCH_CHECK(x.dim() == 2 && (reduce || x.size(0) > 0), reduce ? "x must be [N, H]" : "x must be a non-empty [N, H]");
   const int64_t N = x.size(0), H = x.size(1);
   TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
   const bool bf = act_dtype(x, "x");
-  auto part = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, x.options().dtype(torch::kFloat32));
-  p2fused::column_sum(bf, x.data_ptr(), part.data_ptr<float>(), nullptr, nullptr, int(N), int(H), stream());
-  return part;
+  auto opt = x.options().dtype(torch::kFloat32);
+  torch::Tensor part, out;
+  if (reduce) out = torch::empty({H}, bf16_out ? x.options().dtype(torch::kBFloat16) : opt);
+  if (N > 0) {
+    part = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, opt);
+    p2fused::column_sum(bf, x.data_ptr(), part.data_ptr<float>(), reduce && !bf16_out ? out.data_ptr<float>() : nullptr,
+                        reduce && bf16_out ? bf16_ptr(out) : nullptr, int(N), int(H), stream());
+  } else {
+    out.zero_();
+  }
+  return reduce ? out : part;
 }
+
+torch::Tensor column_sum(torch::Tensor x, bool bf16_out) { return column_sum_any(x, bf16_out, true); }
+
+torch::Tensor column_sum_parts(torch::Tensor x) { return column_sum_any(x, false, false); }
 
 // parts[i] = the [S, H] column partials of xs[i] (bf16 [N, H], N > 0), many per launch
 void column_sum_parts_multi(std::vector<torch::Tensor> xs, std::vector<torch::Tensor> parts) {
@@ -198,16 +244,14 @@ void column_sum_parts_multi(std::vector<torch::Tensor> xs, std::vector<torch::Te
   for (size_t i = 0; i < xs.size(); ++i) {
     const auto& x = xs[i];
     const auto& pt = parts[i];
-    TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
-                    x.stride(0) == x.size(1) && x.size(0) > 0 && x.size(1) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-                "column_sum_parts_multi: xs must be contiguous, 16-byte aligned bf16 [N, H] (H % 8 == 0)");
+    check_bf16(x, "column_sum_parts_multi: xs[i]");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) > 0 && x.size(1) % 8 == 0,
+                "column_sum_parts_multi: xs must be non-empty [N, H] (H % 8 == 0)");
     const int N = int(x.size(0)), H = int(x.size(1)), S = p2fused::bias_gelu_bwd_splits(N);
     TORCH_CHECK(pt.is_cuda() && pt.scalar_type() == torch::kFloat32 && pt.is_contiguous() && pt.dim() == 2 &&
                     pt.size(0) == S && pt.size(1) == H && pt.device() == x.device() && x.device() == xs[0].device(),
                 "column_sum_parts_multi: parts[i] must be contiguous fp32 [bias_gelu_bwd_splits(N), H] on xs' device");
-    jobs.j[jobs.n++] = p2fused::CsJob{reinterpret_cast<const uint16_t*>(x.data_ptr<at::BFloat16>()),
-                                      pt.data_ptr<float>(), N, H, S, 0};
+    jobs.j[jobs.n++] = p2fused::CsJob{bf16_ptr(x), pt.data_ptr<float>(), N, H, S, 0};
     if (jobs.n == p2fused::kCsMaxJobs || i + 1 == xs.size()) {
       p2fused::colsum_multi(jobs, stream());
       jobs.n = 0;
@@ -234,8 +278,7 @@ void col_reduce_multi(std::vector<torch::Tensor> parts, std::vector<torch::Tenso
                 "col_reduce_multi: outs must be contiguous fp32 / bf16 [C] matching their partials");
     const bool bf = o.scalar_type() == torch::kBFloat16;
     jobs.j[jobs.n++] = p2fused::CrJob{a.data_ptr<float>(), bf ? nullptr : o.data_ptr<float>(), nullptr, nullptr,
-                                      bf ? reinterpret_cast<uint16_t*>(o.data_ptr<at::BFloat16>()) : nullptr,
-                                      int(a.size(0)), int(a.size(1)), 0, 0};
+                                      bf ? bf16_ptr(o) : nullptr, int(a.size(0)), int(a.size(1)), 0, 0};
     if (jobs.n == p2fused::kCrMaxJobs || i + 1 == parts.size()) {
       p2fused::col_reduce_multi(jobs, stream());
       jobs.n = 0;
@@ -245,73 +288,28 @@ void col_reduce_multi(std::vector<torch::Tensor> parts, std::vector<torch::Tenso
 
 torch::Tensor split_sum_bf16(torch::Tensor parts) {
   const c10::DeviceGuard g(parts.device());
-  TORCH_CHECK(parts.is_cuda() && parts.scalar_type() == torch::kBFloat16 && parts.is_contiguous() && parts.dim() >= 2,
-              "parts must be a contiguous bf16 [S, ...] GPU tensor");
+  check_bf16(parts, "parts");
+  TORCH_CHECK(parts.dim() >= 2, "parts must be [S, ...]");
   const int64_t S = parts.size(0), n = parts.numel() / std::max<int64_t>(S, 1);
   TORCH_CHECK(S >= 1 && n % 8 == 0, "split_sum_bf16: S >= 1 and a multiple-of-8 slice required");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(parts.data_ptr()) % 16 == 0, "parts must be 16-byte aligned");
   auto out = torch::empty(parts.sizes().slice(1), parts.options());
-  if (n > 0)
-    p2fused::split_sum_bf16(reinterpret_cast<const uint16_t*>(parts.data_ptr<at::BFloat16>()),
-                            reinterpret_cast<uint16_t*>(out.data_ptr<at::BFloat16>()), n, int(S), stream());
+  if (n > 0) p2fused::split_sum_bf16(bf16_ptr(parts), bf16_ptr(out), n, int(S), stream());
   return out;
 }
 
-torch::Tensor column_sum(torch::Tensor x, bool bf16_out) {
-  const c10::DeviceGuard g(x.device());
-  TORCH_CHECK(x.dim() == 2, "x must be [N, H]");
-  const int64_t N = x.size(0), H = x.size(1);
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  const bool bf = act_dtype(x, "x");
-  auto opt = x.options().dtype(torch::kFloat32);
-  auto out = torch::empty({H}, bf16_out ? x.options().dtype(torch::kBFloat16) : opt);
-  if (N > 0) {
-    auto part = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, opt);
-    p2fused::column_sum(bf, x.data_ptr(), part.data_ptr<float>(), bf16_out ? nullptr : out.data_ptr<float>(),
-                        bf16_out ? reinterpret_cast<uint16_t*>(out.data_ptr<at::BFloat16>()) : nullptr, int(N), int(H),
-                        stream());
-  } else {
-    out.zero_();
-  }
-  return out;
-}
-
-torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor b) {
-  const c10::DeviceGuard g(x.device());
-  const int64_t H = x.size(-1);
-  TORCH_CHECK(H % 8 == 0, "last dim must be a multiple of 8");
-  const bool bf = act_dtype(x, "x");
-  check_f32(b, H, "bias");
-  auto y = torch::empty_like(x);
-  if (x.numel() > 0) p2fused::bias_gelu_fwd(bf, x.data_ptr(), b.data_ptr<float>(), y.data_ptr(), x.numel(), int(H), stream());
-  return y;
-}
-
-std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor b) {
-  const c10::DeviceGuard g(x.device());
-  const int64_t H = x.size(-1), N = x.numel() / H;
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type(), "dy must match x");
-  const bool bf = act_dtype(x, "x");
-  act_dtype(dy, "dy");
-  check_f32(b, H, "bias");
-  auto dx = torch::empty_like(x);
-  auto db = torch::empty({H}, x.options().dtype(torch::kFloat32));  // col_reduce writes every column
-  if (N > 0) {
-    auto pdb = torch::empty({p2fused::bias_gelu_bwd_splits(int(N)), H}, x.options().dtype(torch::kFloat32));
-    p2fused::bias_gelu_bwd(bf, dy.data_ptr(), x.data_ptr(), b.data_ptr<float>(), dx.data_ptr(), pdb.data_ptr<float>(),
-                           db.data_ptr<float>(), int(N), int(H), stream());
-  } else {
-    db.zero_();
-  }
-  return {dx, db};
+// ---- softmax cross-entropy --------------------------------------------------------
+// logits [N, K] and their int64 labels [N]; the forward and the backward binding
+bool xent_check(const torch::Tensor& z, const torch::Tensor& y) {
+  TORCH_CHECK(z.dim() == 2, "logits must be [N, K]");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == torch::kInt64 && y.is_contiguous() && y.numel() == z.size(0) &&
+                  y.device() == z.device(),
+              "labels must be int64 [N] on the logits' GPU");
+  return act_dtype(z, "logits");
 }
 
 std::vector<torch::Tensor> xent_fwd(torch::Tensor z, torch::Tensor y) {
   const c10::DeviceGuard g(z.device());
-  TORCH_CHECK(z.dim() == 2, "logits must be [N, K]");
-  TORCH_CHECK(y.is_cuda() && y.scalar_type() == torch::kInt64 && y.is_contiguous() && y.numel() == z.size(0),
-              "labels must be int64 [N] on the GPU");
-  const bool bf = act_dtype(z, "logits");
+  const bool bf = xent_check(z, y);
   const int64_t N = z.size(0), K = z.size(1);
   auto opt = z.options().dtype(torch::kFloat32);
   auto loss = torch::empty({N}, opt), lse = torch::empty({N}, opt);
@@ -321,7 +319,7 @@ std::vector<torch::Tensor> xent_fwd(torch::Tensor z, torch::Tensor y) {
 
 torch::Tensor xent_bwd(torch::Tensor z, torch::Tensor y, torch::Tensor lse, torch::Tensor gscale) {
   const c10::DeviceGuard g(z.device());
-  const bool bf = act_dtype(z, "logits");
+  const bool bf = xent_check(z, y);
   const int64_t N = z.size(0), K = z.size(1);
   check_f32(lse, N, "lse");
   check_f32(gscale, 1, "grad");
@@ -334,9 +332,8 @@ torch::Tensor xent_bwd(torch::Tensor z, torch::Tensor y, torch::Tensor lse, torc
 
 // ---- fused attention over the QKV projection output --------------------------
 p2attn::AttnShape attn_shape(const torch::Tensor& qkv, int64_t heads) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 3,
-              "qkv must be a contiguous bf16 [B, T, 3C] GPU tensor");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "qkv must be 16-byte aligned");
+  check_bf16(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, T, 3C]");
   const int64_t B = qkv.size(0), T = qkv.size(1), C3 = qkv.size(2);
   TORCH_CHECK(C3 % 3 == 0 && heads > 0 && (C3 / 3) == heads * p2attn::kHeadDim, "qkv last dim must be 3 * heads * 64");
   TORCH_CHECK(T >= 1 && T <= p2attn::kMaxT, "attention kernel supports 1..256 tokens");
@@ -359,9 +356,7 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads) {
   const auto sh = attn_shape(qkv, heads);
   auto o = torch::empty({qkv.size(0), qkv.size(1), int64_t(sh.C)}, qkv.options());
   auto lse = torch::empty({qkv.size(0), heads, qkv.size(1)}, qkv.options().dtype(torch::kFloat32));
-  if (sh.B > 0)
-    p2attn::attention_fwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<uint16_t*>(o.data_ptr()),
-                          lse.data_ptr<float>(), sh, stream());
+  if (sh.B > 0) p2attn::attention_fwd(bf16_ptr(qkv), bf16_ptr(o), lse.data_ptr<float>(), sh, stream());
   return {o, lse};
 }
 
@@ -369,19 +364,16 @@ torch::Tensor attn_bwd(torch::Tensor qkv, torch::Tensor o, torch::Tensor dout, t
   const c10::DeviceGuard g(qkv.device());
   const auto sh = attn_shape(qkv, heads);
   for (auto* t : {&o, &dout}) {
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == torch::kBFloat16 && t->dim() == 3 &&
-                    t->size(0) == sh.B && t->size(1) == sh.T && t->size(2) == sh.C,
-                "o / dout must be contiguous bf16 [B, T, C]");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "o / dout must be 16-byte aligned");
+    check_bf16(*t, "o / dout");
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == sh.B && t->size(1) == sh.T && t->size(2) == sh.C,
+                "o / dout must be [B, T, C]");
   }
   TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == torch::kFloat32 &&
                   lse.numel() == int64_t(sh.B) * sh.H * sh.T,
               "lse must be the forward's fp32 [B, H, T]");
   auto dqkv = torch::empty_like(qkv);
   if (sh.B > 0)
-    p2attn::attention_bwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<const uint16_t*>(o.data_ptr()),
-                          reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
-                          reinterpret_cast<uint16_t*>(dqkv.data_ptr()), sh, stream());
+    p2attn::attention_bwd(bf16_ptr(qkv), bf16_ptr(o), bf16_ptr(dout), lse.data_ptr<float>(), bf16_ptr(dqkv), sh, stream());
   return dqkv;
 }
 

@@ -171,19 +171,17 @@ class _LayerNorm(torch.autograd.Function):
         return dx.view(ctx.shape), dw, db, None
 
 
+def _ln_native(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """What the LayerNorm kernels take: a native activation of C % 8 == 0, C <= 2048 columns, an fp32 weight."""
+    C = x.shape[-1]
+    return _native(x) and weight.dtype == torch.float32 and C % 8 == 0 and C <= 2048
+
+
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """LayerNorm over the last dim; output dtype = input dtype (statistics in fp32)."""
-    C = x.shape[-1]
-    if (
-        _native(x)
-        and weight is not None
-        and bias is not None
-        and weight.dtype == torch.float32
-        and C % 8 == 0
-        and C <= 2048
-    ):
+    if weight is not None and bias is not None and _ln_native(x, weight):
         return _LayerNorm.apply(x, weight, bias, eps)
-    return F.layer_norm(x, (C,), weight, bias, eps)
+    return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
 
 
 # -- residual add + LayerNorm -----------------------------------------------------
@@ -218,11 +216,10 @@ def add_layer_norm_reference(x, r, w, b, eps):
 
 def add_layer_norm(x: torch.Tensor, r: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5):
     """``s = x + r; return s, LayerNorm(s)`` in one pass (one pass back: dx = dr = ds + LN'(dy))."""
-    C = x.shape[-1]
-    if _native(x) and r.shape == x.shape and weight.dtype == torch.float32 and C % 8 == 0 and C <= 2048:
+    if _ln_native(x, weight) and r.shape == x.shape:
         return _AddLayerNorm.apply(x, r, weight, bias, eps)
     s = x + r
-    return s, F.layer_norm(s, (C,), weight, bias, eps)
+    return s, F.layer_norm(s, (x.shape[-1],), weight, bias, eps)
 
 
 # -- linear with a fused bias gradient -------------------------------------------------
@@ -253,7 +250,6 @@ def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     if part.dtype == torch.bfloat16 and (N * K) % 8 == 0:
         return _fx().split_sum_bf16(part)  # one pass, fp32 accumulation, bf16 out
     return part.sum(0, dtype=torch.float32).to(dy2.dtype)
-
 
 
 class _Linear(torch.autograd.Function):
@@ -344,7 +340,7 @@ def softmax_xent(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return F.cross_entropy(logits, labels)
 
 
-# -- multi-head self-attention --------------------------------------------------------
+# -- ViT embedding ---------------------------------------------------------------------
 class _EmbedTokens(torch.autograd.Function):
     """``cat([cls, y], 1) + pos`` of a ViT in one kernel each way (``csrc/fused_ops.hip``
     embed_tokens_*): the backward writes the patch tokens' gradient contiguously for the
@@ -374,6 +370,7 @@ def patchify_u8(x: torch.Tensor, patch: int) -> torch.Tensor:
     return _fx().patchify_u8(x.contiguous(), int(patch))
 
 
+# -- multi-head self-attention --------------------------------------------------------
 class _AttentionQKV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, heads):

@@ -75,7 +75,9 @@ chunk (columns >= C) and the first chunk is the K = 1 layout, so every output ke
 register count changes.  8b moves the same boundary the harmful way (columns 512 .. 519 fall out of
 the row) and is caught at C = 520.
 
-Not covered: the R > 1 instantiations of ln_fwd_kernel (unreachable: ``multi`` is a constant false).
+The backward bindings check what their forward checks (one check per op in csrc/fused_bindings.cpp):
+test_backward_bindings_refuse_what_the_forward_refuses holds them to it on inputs the kernels were
+never written for, so every case there must be refused by the binding, before any launch.
 """
 
 from __future__ import annotations
@@ -523,6 +525,71 @@ def test_softmax_xent_label_out_of_range(K, lab, dtype):
     y[3] = K if lab == "K" else lab
     bad = torch.arange(N) == 3
     _xent_check(f"xent label {lab}", _dev(fc.xent_logits("standard", N, K), dtype), y.to(DEV), bad_labels=bad)
+
+
+# ----------------------------------------------------------------------------
+# the backward bindings: the forward's checks, and one body per reducing / _parts pair
+# ----------------------------------------------------------------------------
+def _refused(call, message):
+    """The binding's own check refuses the call (its message, not a HIP error): nothing was launched."""
+    with pytest.raises(RuntimeError, match=message):
+        call()
+
+
+def test_backward_bindings_refuse_what_the_forward_refuses():
+    """Inputs outside the kernels' contract, at most [3, 2056]: each backward binding raises its shape / dtype
+    check before any launch, as its forward does, and no HIP error is left pending."""
+    N = 3
+    bf = torch.bfloat16
+
+    def ln(C, gs=None, dim1=False):
+        shape = (C,) if dim1 else (N, C)
+        x, dy = torch.ones(shape, device=DEV, dtype=bf), torch.ones(shape, device=DEV, dtype=bf)
+        st = torch.ones(N, device=DEV)
+        return dy, x, torch.ones(C, device=DEV), st, st, gs
+
+    misaligned = torch.ones(N * 8 + 8, device=DEV, dtype=bf)[1:N * 8 + 1].view(N, 8)  # 2 bytes past a 16-byte boundary
+    strided = torch.ones(8, N, device=DEV, dtype=bf).t()
+    assert misaligned.is_contiguous() and misaligned.data_ptr() % 16 == 2 and not strided.is_contiguous()
+    for f in (fx().ln_bwd, fx().ln_bwd_parts):
+        _refused(lambda: f(*ln(fc.LN_CS[-1] + 8)), "C must be a multiple of 8 and <= 2048")
+        _refused(lambda: f(*ln(12)), "C must be a multiple of 8")
+        _refused(lambda: f(*ln(16, dim1=True)), r"x must be \[N, C\]")
+        _refused(lambda: f(*ln(8, misaligned)), "gsum must be 16-byte aligned")
+        _refused(lambda: f(*ln(8, strided)), "gsum must be a contiguous GPU tensor")
+    x12 = torch.ones(N, 12, device=DEV, dtype=bf)
+    for f in (fx().bias_gelu_bwd, fx().bias_gelu_bwd_parts):
+        _refused(lambda: f(x12, x12, torch.ones(12, device=DEV)), "last dim must be a multiple of 8")
+    z = torch.ones(N, 8, device=DEV)
+    lse, g = torch.ones(N, device=DEV), torch.ones(1, device=DEV)
+    y = torch.zeros(N, dtype=torch.int64, device=DEV)
+    _refused(lambda: fx().xent_bwd(z, y.int(), lse, g), "labels must be int64")
+    _refused(lambda: fx().xent_bwd(z, y.cpu(), lse, g), "labels must be int64")
+    _refused(lambda: fx().xent_bwd(z, torch.zeros(N + 1, dtype=torch.int64, device=DEV), lse, g), "labels must be int64")
+    _refused(lambda: fx().xent_bwd(z[0].contiguous(), y[:1], lse, g), r"logits must be \[N, K\]")
+    # a pending HIP error would fail torch's next launch check or this synchronise
+    assert float(torch.ones(4, device=DEV).add_(1).sum()) == 8.0
+    torch.cuda.synchronize()
+
+
+def test_reducing_and_parts_backward_are_bitwise_equal():
+    """ln_bwd, bias_gelu_bwd and column_sum against their _parts call followed by col_reduce_multi: every output
+    equal.  Each pair is one body in the bindings; this pins the rule the two share."""
+    for dtype in DTYPES:
+        for N, C in ((5, 520), (17, 8)):
+            for res in (False, True):
+                x, r, w, b, dy, gs = _ln_case(N, C, "standard", 1e-5, dtype, res)
+                _, mean, rstd = fx().ln_fwd(x, w, b, 1e-5)
+                dx, dw, db = fx().ln_bwd(dy, x, w, mean, rstd, gs)
+                dx2, pdw, pdb = fx().ln_bwd_parts(dy, x, w, mean, rstd, gs)
+                assert torch.equal(dx2, dx) and torch.equal(_reduce_single(pdw), dw) and torch.equal(_reduce_single(pdb), db)
+        x, _, w, _, dy, _ = _ln_case(33, 520, "standard", 1e-5, dtype, False)
+        dx, db = fx().bias_gelu_bwd(dy, x, w)
+        dx2, pdb = fx().bias_gelu_bwd_parts(dy, x, w)
+        assert torch.equal(dx2, dx) and torch.equal(_reduce_single(pdb), db)
+        x = _dev(fc.standard((33, 24), "rp"), dtype)
+        for bf16_out in (False, True):
+            assert torch.equal(_reduce_single(fx().column_sum_parts(x), bf16_out), fx().column_sum(x, bf16_out))
 
 
 # ----------------------------------------------------------------------------
